@@ -90,6 +90,7 @@ EVENT_STRIDE = 8      # per-launch HIP events of the timed region: one first-pro
 # (MI355X_MICROARCH.md, MFMA table, I8 row): 256 x 4 x 2048 x 2.4 GHz
 PEAK_I8_MFMA_TOPS = 5033.0
 I8_OPS_PER_PRODUCT = 45 * 2.0      # per N^3: 15 digit pairs x 3 real products (ozaki.hip), 2 ops per MAC
+DUMP_LIMIT_BYTES = 64 * 10 ** 6    # --dump-outputs: everything written, in all
 
 
 def parse(argv=None):
@@ -129,7 +130,32 @@ def parse(argv=None):
     ap.add_argument("--no-kernel-events", action="store_true", help="no per-launch HIP events in the timed region")
     ap.add_argument("--kernel-table", action="store_true",
                     help="HIP events around every hot-path launch; per-kernel table on stderr (diagnostic)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed on rank 0 as DIR/<name>.npy: the final state "
+                         "(W_real, W_imag; float64, float32 with --dtype c64) and the numeric step statistics the "
+                         "stepper returned (float64).  A state above the %d MB budget is written as a fixed sample "
+                         "(seed 0) of its entries, their flat indices in W_index" % (DUMP_LIMIT_BYTES // 10 ** 6))
     return ap.parse_args(argv)
+
+
+def dump_outputs(directory, W, stats):
+    """What a caller of the timed path receives -- the state after its last step and the statistics of the call -- as
+    .npy files of at most DUMP_LIMIT_BYTES in all.  The inputs are seeded (make_W0(N, rank)), so two builds run with the
+    same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    part = np.float32 if W.dtype == np.complex64 else np.float64
+    itemsize = np.dtype(part).itemsize
+    budget = DUMP_LIMIT_BYTES - (1 << 20)          # the statistics are a few scalars
+    if 2 * W.size * itemsize > budget:
+        idx = np.unique(np.random.default_rng(0).integers(0, W.size, budget // (2 * itemsize + 8)))
+        W = W.reshape(-1)[idx]
+        np.save(os.path.join(directory, "W_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "W_real.npy"), np.ascontiguousarray(W.real, dtype=part))
+    np.save(os.path.join(directory, "W_imag.npy"), np.ascontiguousarray(W.imag, dtype=part))
+    for key, v in sorted(stats.items()):
+        if isinstance(v, (int, float, np.integer, np.floating)):
+            np.save(os.path.join(directory, key + ".npy"), np.array([v], dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -802,9 +828,6 @@ def _load_injected_trajectory():
 
 
 def main():
-    # (read by the HIP runtime when it initialises -- under torch.distributed.run that is torch's doing,
-    # before quflow_amd is imported: see quflow_amd/__init__.py and DESIGN.md 4d)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -1014,6 +1037,8 @@ def main():
         scratch = None
     if events:
         _lib.check(lib.qf_profile_enable(h, 0))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr.download(), st)
 
     elapsed = elapsed_rank
     rank_rates = [args.steps / elapsed_rank]

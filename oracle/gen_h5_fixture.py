@@ -21,6 +21,15 @@ Writes (data only -- no reference source travels):
                                              resume through quflow_amd must reproduce
   tests/golden/ref_qusim_n16_datapath.hdf5   the same first run under datapath "/run1/" with a (2,N,N)
                                              state stack and default loggers -- group handling
+  tests/golden/ref_qusim_n16_datapath_W0.npz the state stack that run started from (W0 here and W0 of
+                                             the _continued file are the stored initial states: make_W0
+                                             recomputed on another machine may differ in the last bit)
+  tests/golden/h5store_n16.hdf5              direction 2: a file quflow_amd.Simulation (H5Store) wrote
+                                             (N = 16, qutypes mat + shr, loggers normL2 / enstrophy, 20
+                                             steps in two chunks of 10, the oracle's stepper) ...
+  tests/golden/h5store_n16_resumed_by_reference.hdf5
+                                             ... and the same file after the REFERENCE's QuSimulation
+                                             opened it and its solve appended 20 more steps (rows 3, 4)
 """
 import os
 import shutil
@@ -69,6 +78,32 @@ def first_run(path, W0, datapath="/", loggers=True):
     return sim
 
 
+def h5store_fixture(N=16):
+    """Direction 2 of the interop: the reference opens and resumes a file this package wrote.  Both states of the file
+    are kept, so that the test runs without the reference: a file written now must have the layout the reference
+    accepted, and the rows the reference appended must read back through quflow_amd."""
+    sys.path.insert(0, REPO)
+    import quflow_amd as qfa
+    from oracle import isomp_oracle as oracle, quantization_oracle as qo
+    qfa.quantization.mat2shr = qo.mat2shr          # 'shr' rows without a GPU (the device transform has its own tests)
+    tmp = tempfile.mkdtemp(prefix="qf_h5_fixture_")
+    try:
+        path = os.path.join(tmp, "h5store_n16.hdf5")
+        sim = qfa.Simulation(path, overwrite=True, state=make_W0(N, 21), qutypes={'mat': None, 'shr': None},
+                             loggers={'normL2': qfa.geometry.norm_L2, 'enstrophy': oracle.enstrophy})
+        sim['stepsize'] = 0.25
+        sim['steps'] = 20
+        sim['steps_out'] = 10
+        sim['info'] = "written by quflow_amd.Simulation"
+        qfa.solve(sim, integrator=oracle.isomp, hamiltonian=oracle.solve_poisson, resident=False, progress_bar=False)
+        shutil.copyfile(path, os.path.join(GOLD, "h5store_n16.hdf5"))
+        rsim = qf.QuSimulation(path)
+        qf.solve(rsim, progress_bar=False)
+        shutil.copyfile(path, os.path.join(GOLD, "h5store_n16_resumed_by_reference.hdf5"))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     N = 16
     W0 = make_W0(N, 16)
@@ -95,9 +130,12 @@ def main():
         Wst = np.stack([W0, make_W0(N, 17)])
         first_run(path3, Wst, datapath="/run1/", loggers=False)
         shutil.copyfile(path3, os.path.join(GOLD, "ref_qusim_n16_datapath.hdf5"))
+        np.savez_compressed(os.path.join(GOLD, "ref_qusim_n16_datapath_W0.npz"), W0=Wst)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    for fn in ("ref_qusim_n16.hdf5", "ref_qusim_n16_continued.npz", "ref_qusim_n16_datapath.hdf5"):
+    h5store_fixture(N)
+    for fn in ("ref_qusim_n16.hdf5", "ref_qusim_n16_continued.npz", "ref_qusim_n16_datapath.hdf5", "ref_qusim_n16_datapath_W0.npz",
+               "h5store_n16.hdf5", "h5store_n16_resumed_by_reference.hdf5"):
         p = os.path.join(GOLD, fn)
         print("wrote %-45s %7.1f KiB" % (os.path.relpath(p, REPO), os.path.getsize(p) / 1024))
     with h5py.File(os.path.join(GOLD, "ref_qusim_n16.hdf5"), "r") as f:

@@ -12,14 +12,6 @@ Drop-in for the reference's stepper and Laplacian-backend protocols
 All compute runs in hand-written HIP kernels for gfx950 behind the C ABI of
 include/quflow_hip.h; there is no CPU fallback.
 """
-import os as _os
-
-# The HIP runtime multiplexes its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and gives a
-# new stream the least-used one: with one trajectory alive, a DeviceEnsemble of four more put two of its
-# replicas on ONE queue, where their kernels serialise (measured: sum rate of 4 replicas at N=512 1.43x
-# instead of 1.78x the single-trajectory rate).  Eight queues keep up to seven concurrent trajectories
-# apart.  Read by the runtime when it initialises: set before anything touches HIP; a user's own setting wins.
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from . import laplacian
 from . import integrators

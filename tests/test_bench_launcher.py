@@ -18,8 +18,12 @@ class CpuTrajectory:
     """Oracle-backed stand-in with the DeviceTrajectory interface (tests only)."""
     def __init__(self, W0):
         self.W = W0.copy()
+        self.calls = os.environ.get("QF_TRAJ_CALLS")
 
     def advance(self, dt, steps, **kw):
+        if self.calls:
+            with open(self.calls, "a") as f:
+                f.write("%d\n" % steps)
         stats = {"iterations": 0.0}
         self.W = oracle.isomp(self.W, dt, steps=steps, stats=stats, **kw)
         stats["total_iterations"] = int(round(stats["iterations"] * steps))
@@ -30,6 +34,9 @@ class CpuTrajectory:
 
     def sync(self):
         pass
+
+    def download(self):
+        return self.W.copy()
 '''
 
 
@@ -216,3 +223,53 @@ def test_rehearsal_mode_marks_its_line(tmp_path, oracle):
     assert json.loads([l for l in plain.stdout.splitlines() if l.startswith("{")][0])["config"]["rehearsal"] is None
     short = run_bench(tmp_path, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--N", "16", "--cpu-seconds", "0"], QUFLOW_BENCH_FAKE_GPUS="1")
     assert short.returncode == 2 and "only 1 GPU(s) visible" in short.stderr
+
+
+def test_dump_outputs_writes_the_timed_steps_result(tmp_path, oracle):
+    """--dump-outputs DIR: the state after the last timed step (real and imaginary parts) and the step statistics, as
+    float64 .npy files; --steps is the number of timed steps, ms_per_step the time of one; the same arguments twice give
+    the same files."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        calls = tmp_path / ("calls%d.txt" % run)
+        out = tmp_path / ("out%d" % run)
+        res = run_bench(tmp_path, ["--steps", "3", "--warmup", "2", "--N", "16", "--cpu-seconds", "0", "--dump-outputs", str(out)],
+                        QF_TRAJ_CALLS=str(calls))
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert calls.read_text().split() == ["2", "3"]                  # warm-up, then the timed steps
+        files = sorted(os.listdir(out))
+        assert {"W_real.npy", "W_imag.npy", "iterations.npy"} <= set(files) and "W_index.npy" not in files
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f], err_msg=f)
+    dt = 0.25 * oracle.hbar(16)
+    W = oracle.isomp(oracle.isomp(oracle.make_W0(16, 0), dt, steps=2), dt, steps=3)
+    np.testing.assert_array_equal(dumps[0]["W_real.npy"] + 1j * dumps[0]["W_imag.npy"], W)
+
+
+def test_dump_outputs_samples_a_state_above_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 << 20)
+    rng = np.random.default_rng(1)
+    W = rng.standard_normal((512, 512)) + 1j * rng.standard_normal((512, 512))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), W, {"iterations": 2.5, "note": "not numeric"})
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_LIMIT_BYTES
+    assert sorted(os.listdir(tmp_path / "a")) == ["W_imag.npy", "W_index.npy", "W_real.npy", "iterations.npy"]
+    idx = np.load(tmp_path / "a" / "W_index.npy")
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "b" / "W_index.npy"))     # a fixed sample
+    assert idx.dtype == np.float64 and len(idx) > 10000 and np.all(np.diff(idx) > 0) and idx[-1] < W.size
+    flat = W.reshape(-1)[idx.astype(np.int64)]
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "W_real.npy"), flat.real)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "W_imag.npy"), flat.imag)
+    assert np.load(tmp_path / "a" / "iterations.npy").tolist() == [2.5]

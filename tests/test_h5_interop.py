@@ -7,16 +7,17 @@
   direction 1 (any interpreter with h5py): quflow_amd.Simulation opens the reference's file, reads every dataset,
               attribute and pickled argument, resumes and appends; the appended rows are what the reference's own
               resume produced, and bit-identical to the same stepper run straight from the stored row;
-  direction 2 (needs the reference too: build container only): the reference's QuSimulation opens a file that
-              quflow_amd.Simulation (H5Store) wrote, reads it, resumes and appends to it, and quflow_amd reads the result.
+  direction 2: the reference's QuSimulation opened a file that quflow_amd.Simulation (H5Store) wrote, resumed and
+              appended to it (`h5store_n16*.hdf5`, both states of that file): a file written now has the layout the
+              reference accepted, and quflow_amd reads the result.
 
 h5py lives only under /opt/conda/bin/python3.9 in this image: under the default interpreter this module skips, and
 tests/test_h5_interop_runner.py runs it in that interpreter.  The stepper here is the oracle's (CPU checker); the
 device-resident resume of the same file is tests/test_h5_interop_runner.py::test_device_resume_of_reference_written_file.
 """
 import os
+import pickle
 import shutil
-import sys
 
 import numpy as np
 import pytest
@@ -29,8 +30,6 @@ import quflow_amd as qfa  # noqa: E402
 from quflow_amd.simulation import Simulation, solve  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = os.environ.get("QUFLOW_REFERENCE", "/root/reference")
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 16
 
 
@@ -51,7 +50,7 @@ def host_transforms(monkeypatch):
 
 
 def test_open_reference_written_file(ref_file, oracle, host_transforms):
-    W0 = oracle.make_W0(N, 16)
+    W0 = np.load(os.path.join(GOLDEN, "ref_qusim_n16_continued.npz"))["W0"]      # the state the reference's run started from
     sim = Simulation(ref_file)
     fields = sim.fieldnames
     assert fields['mat'] == ((3, N, N), np.dtype(np.complex128))
@@ -153,8 +152,9 @@ def test_reference_file_with_datapath_and_state_stack(tmp_path, oracle, host_tra
     f = sim.fieldnames
     assert f['mat'] == ((3, 2, N, N), np.dtype(np.complex128)) and f['shr'] == ((3, 2, N * N), np.dtype(np.float64))
     assert set(f) == {'mat', 'shr', 'time', 'step', 'tol_auto', 'iterations', 'number_of_maxit'}
-    np.testing.assert_array_equal(sim['mat', 0, 0], oracle.make_W0(N, 16))
-    np.testing.assert_array_equal(sim['mat', 0, 1], oracle.make_W0(N, 17))
+    W0 = np.load(os.path.join(GOLDEN, "ref_qusim_n16_datapath_W0.npz"))["W0"]     # the stack the reference's run started from
+    np.testing.assert_array_equal(sim['mat', 0, 0], W0[0])
+    np.testing.assert_array_equal(sim['mat', 0, 1], W0[1])
     assert sim.loggers == {} and int(sim['N']) == N
     # append one row by hand (the callback protocol), as solve would
     Wn = sim['mat', -1]
@@ -189,31 +189,27 @@ def test_default_qutypes_of_the_reference_are_refused_on_append_only(tmp_path, o
 
 
 # ------------------------------------------------------------------------------------------------
-# direction 2: the reference reads and continues a file this package wrote (build container only)
+# direction 2: the reference reads and continues a file this package wrote
 # ------------------------------------------------------------------------------------------------
 
-@pytest.fixture
-def reference():
-    if not os.path.isdir(os.path.join(REF, "quflow")):
-        pytest.skip("the reference is not mounted here (build container only)")
-    shim = os.path.join(REPO, "oracle", "refshim")
-    saved = list(sys.path)
-    os.environ["QUFLOW_SAVE_COMPUTED_BASIS"] = "0"
-    sys.path.insert(0, shim)              # numba / appdirs / ducc0 stand-ins; the real h5py is imported already
-    sys.path.insert(0, REF)
-    sys.dont_write_bytecode = True
-    try:
-        import quflow as qf
-        assert qf.simulation.h5py is h5py
-        yield qf
-    finally:
-        sys.path[:] = saved
+def h5_layout(path):
+    """Everything the reference's QuSimulation reads from a file besides the rows: datasets (dtype, shape, maxshape, chunks),
+    the attributes of the data path and of args/ (simulation.py:150-166, 236-276); 'created' is a time stamp."""
+    with h5py.File(path, "r") as f:
+        datasets = {k: (f[k].dtype, f[k].shape, f[k].maxshape, f[k].chunks) for k in f.keys() if isinstance(f[k], h5py.Dataset)}
+        attrs = {k: (type(v), np.asarray(v).tobytes()) for k, v in f["/"].attrs.items() if k != "created"}
+        args = {k: (type(v), np.asarray(v).tobytes()) for k, v in f["/args"].attrs.items()}
+    return datasets, attrs, args
 
 
-def test_reference_reads_and_continues_a_file_written_by_h5store(tmp_path, oracle, host_transforms, reference):
-    qf = reference
+def test_reference_reads_and_continues_a_file_written_by_h5store(tmp_path, oracle, host_transforms):
+    """h5store_n16.hdf5 is a file quflow_amd.Simulation wrote, h5store_n16_resumed_by_reference.hdf5 the same file after the
+    reference's QuSimulation opened it and its solve appended 20 steps (oracle/gen_h5_fixture.py).  A file written now must
+    be the one the reference accepted, and what the reference appended must read back here."""
+    accepted = os.path.join(GOLDEN, "h5store_n16.hdf5")
+    with h5py.File(accepted, "r") as f:
+        W0 = f["mat"][0]
     path = str(tmp_path / "ours.hdf5")
-    W0 = oracle.make_W0(N, 21)
     dt = 0.25 * oracle.hbar(N)
     sim = Simulation(path, overwrite=True, state=W0, qutypes={'mat': None, 'shr': None},
                      loggers={'normL2': qfa.geometry.norm_L2, 'enstrophy': oracle.enstrophy})
@@ -223,27 +219,24 @@ def test_reference_reads_and_continues_a_file_written_by_h5store(tmp_path, oracl
     sim['info'] = "written by quflow_amd.Simulation"
     solve(sim, integrator=oracle.isomp, hamiltonian=oracle.solve_poisson, resident=False, progress_bar=False)
     ours = {name: sim[name] for name in sim.fieldnames}
-
-    rsim = qf.QuSimulation(path)                      # the reference opens it (simulation.py:150-166)
-    assert rsim.qutypes == {'mat': None, 'shr': None}
-    assert set(rsim.loggers) == {'normL2', 'enstrophy'}
-    assert set(rsim.fieldnames) == set(ours)
+    assert h5_layout(path) == h5_layout(accepted)
+    with h5py.File(accepted, "r") as f:
+        written = {name: f[name][:] for name in f.keys() if isinstance(f[name], h5py.Dataset)}
+    assert set(written) == set(ours)
     for name in ours:
-        np.testing.assert_array_equal(rsim[name], ours[name], err_msg=name)
-        assert rsim.fieldnames[name] == (ours[name].shape, ours[name].dtype), name
-    np.testing.assert_array_equal(rsim['mat', -1], ours['mat'][-1])
-    assert int(rsim['N']) == N and rsim['info'] == "written by quflow_amd.Simulation"
-    assert dict(rsim.args()).keys() == {'stepsize', 'steps', 'steps_out'}
-    assert float(rsim['stepsize']) == 0.25 and int(rsim['steps_out']) == 10
-    # the reference resumes and appends with its own stepper, solver and transforms (tests/test_simulation.py:130-168)
-    qf.solve(rsim, progress_bar=False)
-    back = Simulation(path)
+        np.testing.assert_allclose(ours[name], written[name], rtol=0, atol=1e-14, err_msg=name)
+
+    # the reference resumed and appended with its own stepper, solver and transforms (tests/test_simulation.py:130-168)
+    resumed = str(tmp_path / "resumed.hdf5")
+    shutil.copyfile(os.path.join(GOLDEN, "h5store_n16_resumed_by_reference.hdf5"), resumed)
+    back = Simulation(resumed)
+    assert back.qutypes == {'mat': None, 'shr': None} and set(back.fieldnames) == set(written)
     assert back.fieldnames['mat'][0] == (5, N, N) and back.fieldnames['shr'][0] == (5, N * N)
     np.testing.assert_array_equal(back['step'], [0, 10, 20, 30, 40])
     np.testing.assert_allclose(back['time'], 10 * dt * np.arange(5), rtol=1e-15)
-    for name in ours:
-        np.testing.assert_array_equal(back[name][:3], ours[name], err_msg=name)
-    Wc = ours['mat'][-1].copy()
+    for name in written:
+        np.testing.assert_array_equal(back[name][:3], written[name], err_msg=name)
+    Wc = written['mat'][-1].copy()
     for r in (3, 4):
         st = {"iterations": 0.0}
         Wc = oracle.isomp(Wc, dt, steps=10, stats=st)
@@ -252,6 +245,7 @@ def test_reference_reads_and_continues_a_file_written_by_h5store(tmp_path, oracl
         np.testing.assert_allclose(back['shr', r], host_transforms.mat2shr(Wc), atol=1e-13)
         assert abs(back['enstrophy', r] - oracle.enstrophy(Wc)) <= 1e-14
         assert abs(back['normL2', r] - qfa.geometry.norm_L2(back['mat', r])) <= 1e-15
-    # a pickled callable of this package is readable by the reference as long as quflow_amd is importable there
+    # a pickled callable of this package is stored the way the reference unpickles it (simulation.py:258-263)
     sim['hamiltonian'] = qfa.geometry.norm_L2
-    assert qf.QuSimulation(path)['hamiltonian'] is qfa.geometry.norm_L2
+    with h5py.File(path, "r") as f:
+        assert pickle.loads(f["/args"].attrs["hamiltonian"][0]) is qfa.geometry.norm_L2

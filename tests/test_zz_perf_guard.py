@@ -107,12 +107,16 @@ def test_four_replicas_share_the_gpu(qfa):
     """four replicas per GPU at N = 512 reach 1.83 - 1.92 x one trajectory -- IF their streams' hardware queues
     sit on four different pipes (queue number mod 4; two replicas on one pipe: 1.1 - 1.2 x, profiles/r06_x4_hardware_queues.txt).
     The members of a DeviceEnsemble are created back to back and the library never uses the NULL stream, so their queues are
-    consecutive whatever the process did before (this suite created hundreds of contexts before this test).  Floor 1.6 x."""
+    consecutive whatever the process did before (this suite created hundreds of contexts before this test).  Floor 1.6 x.
+    The number of hardware queues is the environment's (GPU_MAX_HW_QUEUES, HIP's default 4): with two, the four replicas
+    share two queues on two pipes (measured 1.58 x), floor 1.4 x."""
     from quflow_amd.context import release_contexts
     release_contexts()
     one = _ensemble_rate(qfa, 512, 1, 300)
     four = _ensemble_rate(qfa, 512, 4, 300)
-    print("perf guard: N=512 one trajectory %.0f, four replicas %.0f timesteps/s (%.2f x)" % (one, four, four / one))
+    queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+    print("perf guard: N=512 one trajectory %.0f, four replicas %.0f timesteps/s (%.2f x), %d hardware queues"
+          % (one, four, four / one, queues))
     if os.environ.get("QUFLOW_PERF_GUARD", "1") == "0":
         pytest.skip("QUFLOW_PERF_GUARD=0: timing asserts skipped (%.2f x)" % (four / one))
-    assert four >= 1.6 * one, (one, four)
+    assert four >= (1.6 if queues >= 4 else 1.4) * one, (one, four, queues)
