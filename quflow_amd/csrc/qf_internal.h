@@ -202,6 +202,7 @@ struct qf_c64 {
     double *rowpart = nullptr;                 // [column tiles of 64][N] partial row sums of the second product
     int rowpart_tiles = 0;
     int dw_cur = 0;
+    bool increment_is_zero = true;             // (as qf_ctx's)
     bool increment_valid = false;
     float2 *W2 = nullptr, *Whalf2 = nullptr;   // fused step end: second buffers of the W / Whalf pairs (on demand)
     // upper-triangle second product (k_cgemm_tri): exchange area [tiles][4][64*64], arrival counters [tiles], K pieces
@@ -277,7 +278,6 @@ struct qf_ctx {
     cplx *dW[2] = {nullptr, nullptr};  // iteration vector, ping-pong (cur / new)
     int dw_cur = 0;
     bool increment_is_zero = true; // this call starts from dW = 0 (not a qf_isomp_continue)
-    bool c64_increment_is_zero = true;   // the same for the complex64 buffers
     int pred_first_iters = 0;      // iterations the cold first step of the previous call needed
     bool increment_valid = false;  // dW[dw_cur] holds the increment of the last qf_isomp call (qf_isomp_continue)
     cplx *W2 = nullptr;      // fused protocol: second buffer of the W pair (allocated on demand)
