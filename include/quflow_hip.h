@@ -139,7 +139,12 @@ int qf_isomp_continue(qf_ctx *ctx, double dt, int steps, double tol, int minit, 
  * How many at once: FOUR, created back to back.  The runtime gives every stream the next hardware queue when it is first
  * used and a queue's number mod 4 is the pipe that dispatches it; two replicas on one pipe lose 40 % of their combined rate
  * (N = 512: sum 18,100 timesteps/s for k = 4, 13,000 for k = 5, 16,100 for k = 8).  The call takes any k; the
- * Python mirror passes larger ensembles four contexts at a time. */
+ * Python mirror passes larger ensembles four contexts at a time.
+ * A member that fails (QF_ERR_NONFINITE: its residual turned inf / NaN) does not stop the others: every member runs to its
+ * end, and the call returns the first member's error.  The failed member holds what its own qf_isomp call would leave (the
+ * state after its last completed step) and reports total_iterations = number_of_maxit = -1, last_resnorm = NaN in its
+ * stats_out entry; every other member holds its state after all `steps` steps and its own statistics.  Afterwards every
+ * context is marked as after a failed call (its increment is not carried, its skew check is redone at the next entry). */
 int qf_isomp_multi(qf_ctx **ctxs, int k, double dt, int steps, double tol, int minit, int maxit,
                    qf_isomp_stats *stats_out);
 /* The same for contexts that hold complex64 states (qf_c64_upload_W): each runs the float32 launches qf_c64_isomp would
@@ -385,8 +390,8 @@ int qf_cgemm(qf_ctx *ctx, const void *A_host, const void *B_host, void *C_host);
  * qf_fixedpoint_products, full second product); rowsum: N doubles */
 int qf_c64_fixedpoint_products(qf_ctx *ctx, const void *Phalf_host, const void *Whalf_host, const void *W_host,
                                const void *dW_old_host, void *dW_new_host, void *Whalf_new_host, double *rowsum_host);
-/* The same through the upper-triangle second product (N % 64 == 0, skew-Hermitian operands): the kernel the complex64
- * stepper uses from N = 768 on.  dW comes back completed by its mirror image. */
+/* The same through the upper-triangle second product on 32 x 32 tiles (any N >= 64, skew-Hermitian operands): the kernel the
+ * complex64 stepper uses at every N >= 64 on an exactly skew-Hermitian state.  dW comes back completed by its mirror image. */
 int qf_c64_fixedpoint_products_tri(qf_ctx *ctx, const void *Phalf_host, const void *Whalf_host, const void *W_host,
                                    const void *dW_old_host, void *dW_new_host, void *Whalf_new_host, double *rowsum_host);
 

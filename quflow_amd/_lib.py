@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QUFLOW_HIP_LIB") or os.path.join(_HERE, "libquflow_hip.so")
 
 QF_OK = 0
+QF_ERR_NONFINITE = 7
 ERR_NAMES = {1: "QF_ERR_INVALID", 2: "QF_ERR_NO_DEVICE", 3: "QF_ERR_HIP", 4: "QF_ERR_STATE", 5: "QF_ERR_CALLBACK",
              6: "QF_ERR_UNSUPPORTED", 7: "QF_ERR_NONFINITE"}
 

@@ -927,11 +927,25 @@ int isomp_multi(qf_ctx **ctxs, int k, double dt, int steps, double tol, int mini
         }
         together = together && ctxs[r]->fused_allowed;
     }
+    // a member whose call failed reports total_iterations = number_of_maxit = -1 and a NaN residual; the others report
+    // their own statistics
+    auto mark_failed = [&](int r) {
+        if (!stats_out) return;
+        stats_out[r].total_iterations = -1;
+        stats_out[r].number_of_maxit = -1;
+        stats_out[r].last_resnorm = std::numeric_limits<double>::quiet_NaN();
+    };
     if (!together) {
-        // (QUFLOW_HIP_FUSED=0 / QUFLOW_HIP_GEMM=4m A/B switches): one after the other
-        for (int q = 0; q < k; ++q)
-            QF_TRY(isomp_impl<S>(ctxs[q], dt, steps, tol, minit, maxit, 0, 0, stats_out ? stats_out + q : nullptr, false));
-        return QF_OK;
+        // (QUFLOW_HIP_FUSED=0 / QUFLOW_HIP_GEMM=4m A/B switches): one after the other, every member to its end as below
+        int first_rc = QF_OK;
+        for (int q = 0; q < k; ++q) {
+            const int rc = isomp_impl<S>(ctxs[q], dt, steps, tol, minit, maxit, 0, 0, stats_out ? stats_out + q : nullptr, false);
+            if (rc != QF_OK) {
+                mark_failed(q);
+                if (first_rc == QF_OK) first_rc = rc;
+            }
+        }
+        return first_rc;
     }
     auto abort_all = [&](int rc) {
         for (int q = 0; q < k; ++q) fused_abort(ctxs[q]);
@@ -958,13 +972,16 @@ int isomp_multi(qf_ctx **ctxs, int k, double dt, int steps, double tol, int mini
     for (int r = 0; r < k; ++r) {
         ctxs[r]->pred_iters = runs[r].pred;
         const int rc = fused_leave<S>(ctxs[r], steps, stats_out ? stats_out + r : nullptr);
-        if (rc != QF_OK && first_rc == QF_OK) first_rc = rc;
+        if (rc != QF_OK) {
+            mark_failed(r);
+            if (first_rc == QF_OK) first_rc = rc;
+        }
     }
     return first_rc == QF_OK ? QF_OK : abort_all(first_rc);
 }
 
 // host-in / host-out parity entry of the complex64 products: through the full second product, or (tri) the
-// upper-triangle one (k_cgemm_tri; N % 64 == 0, skew-Hermitian operands)
+// upper-triangle one (k_cgemm_tri32; N >= 64, skew-Hermitian operands)
 int c64_fixedpoint_products(const char *name, bool tri, qf_ctx *ctx, const void *Phalf_host, const void *Whalf_host,
                             const void *W_host, const void *dW_old_host, void *dW_new_host, void *Whalf_new_host,
                             double *rowsum_host)

@@ -1004,20 +1004,41 @@ class DeviceEnsemble:
 
     def advance(self, dt, steps, tol='auto', maxit=10, minit=1):
         """`steps` steps of every member (the semantics of one `integrator(W, dt, steps=...)` call each);
-        returns one stats dict per member."""
+        returns one stats dict per member.
+
+        A member whose residual turns inf / NaN (what raises in the reference's exit test) does not stop the others: every
+        group of members is advanced, every member runs to its end, and then ONE ValueError is raised.  Its `failed`
+        attribute lists the indices of the failed members, its `stats` attribute the per-member stats dicts (a failed
+        member's is {"failed": True, "tol": ...}).  A failed member holds the state its own DeviceTrajectory.advance would
+        leave on that failure (after its last completed step); every other member has advanced all `steps` steps, exactly
+        as alone.  Any other error raises at once."""
         assert minit >= 1, "minit must be at least 1."
         assert maxit >= minit, "maxit must be at minit."
         tol_c = -1.0 if isinstance(tol, str) else float(tol)
         fn = self._lib.qf_c64_isomp_multi if self.c64 else self._lib.qf_isomp_multi
         out = []
+        failed = []
         for g0 in range(0, len(self.members), self.CONCURRENT):
             group = self.members[g0:g0 + self.CONCURRENT]
             k = len(group)
             handles = (ctypes.c_void_p * k)(*[m.ctx.handle for m in group])
             st = (_lib.IsompStats * k)()
-            _lib.check(fn(handles, k, float(dt), int(steps), tol_c, int(minit), int(maxit), st))
-            out += [{"iterations": s.total_iterations / max(steps, 1), "number_of_maxit": s.number_of_maxit / max(steps, 1),
-                     "total_iterations": s.total_iterations, "tol": s.tol_used, "last_resnorm": s.last_resnorm} for s in st]
+            rc = fn(handles, k, float(dt), int(steps), tol_c, int(minit), int(maxit), st)
+            if rc != _lib.QF_ERR_NONFINITE:
+                _lib.check(rc)
+            for r, s in enumerate(st):
+                # (qf_isomp_multi: a member whose call failed reports total_iterations = -1)
+                if rc == _lib.QF_ERR_NONFINITE and s.total_iterations < 0:
+                    failed.append(g0 + r)
+                    out.append({"failed": True, "tol": s.tol_used})
+                    continue
+                out.append({"iterations": s.total_iterations / max(steps, 1), "number_of_maxit": s.number_of_maxit / max(steps, 1),
+                            "total_iterations": s.total_iterations, "tol": s.tol_used, "last_resnorm": s.last_resnorm})
+        if failed:
+            err = ValueError("array must not contain infs or NaNs (DeviceEnsemble members %s)" % ", ".join(map(str, failed)))
+            err.failed = failed
+            err.stats = out
+            raise err
         return out
 
     def diagnostics(self):

@@ -2013,7 +2013,8 @@ def test_sh_requires_basis(qfa):
 def test_single_precision_input_contract(qfa):
     """complex64 in -> complex64 out, in place; the automatic tolerance is the reference's single-precision
     one (reported in stats['tol_auto']) so that the run stops where the reference's does.  The device
-    evaluates in double precision: its result sits within single-precision rounding of the reference's."""
+    evaluates in single precision, as the reference does (csrc/single.hip): its result sits within single-precision
+    rounding of the reference's."""
     g = load_golden("single_precision")
     N = int(g["N"])
     W0 = g["W0"]

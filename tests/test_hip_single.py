@@ -168,7 +168,8 @@ def test_fixedpoint_products_c64(qfa, N):
     assert np.abs(rows - rows_ref).max() <= N * (bound + 4 * EPS32 * np.abs(dW_old).max())
 
 
-@pytest.mark.parametrize("N", [64, 72, 96, 100, 128, 160, 224, 256, 333, 512, 736, 768, 832, 1000, 1001, 1024, 1056, 1536, 2048])
+@pytest.mark.parametrize("N", [64, 72, 96, 100, 128, 160, 224, 256, 333, 512, 736, 768, 832, 1000, 1001, 1024, 1056, 1536, 2048,
+                               2112, 2304, 3072])
 def test_fixedpoint_products_c64_tri(qfa, N):
     """The complex64 second product on the upper triangle of 32 x 32 tiles (k_cgemm_tri32; exact tilings and guarded edge
     tiles), every tile's K range cut into pieces: against numpy in double precision and against the full product; exactly
