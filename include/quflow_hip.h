@@ -261,6 +261,14 @@ int qf_mat2shr(qf_ctx *ctx, const void *W_host, double *omega_host, long long n_
 /* shc2mat_ / mat2shc_, quantization.py:331-396: omega is N^2 complex128 */
 int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host);
 int qf_mat2shc(qf_ctx *ctx, const void *W_host, void *omega_host);
+/* shc2fun / shr2fun (quflow/transforms.py:220-268, 422-438) at bandwidth L (1..8192, independent of ctx->N):
+ * MW grid (L, 2L-1), row-major.  omega_host == NULL: the coefficients the last qf_mat2shr left on ctx
+ * (as qf_shr2mat's NULL).  omega is trimmed or zero-padded to L^2 entries (qf_shr2fun: after dropping a last degree
+ * cut short, which shr2shc leaves zero); berezin != 0 multiplies
+ * coefficient (l, m) by berezin_multipliers(L)[l].  Neither call needs the quantization basis. */
+int qf_shr2fun(qf_ctx *ctx, const double *omega_host, long long n_omega, int L, int berezin, double *f_host);
+/* omega: n_omega complex128; isreal: f_host is double (L, 2L-1) (the m >= 0 half of omega, a real map), else complex128 */
+int qf_shc2fun(qf_ctx *ctx, const void *omega_host, long long n_omega, int L, int berezin, int isreal, void *f_host);
 
 /* ---- diagnostics on the ctx state W: quflow/physics.py:26-38 with
  *      inner_L2 (quflow/geometry.py:72-76) -------------------------------------- */

@@ -19,11 +19,14 @@ from . import physics
 from . import geometry
 from . import ensemble
 from . import quantization
+from . import transforms
 from . import simulation
 from .simulation import Simulation, solve, create_runfile
 QuSimulation = Simulation          # the reference's name (quflow/simulation.py:60): scripts that say qf.QuSimulation run unchanged
 from .quantization import (shr2mat, mat2shr, shc2mat, mat2shc, get_basis, compute_basis, basis_break_index, elm2ind, ind2elm,
                            berezin_multipliers)
+from .transforms import (shr2fun, shc2fun, shr2shc, shc2shr, as_fun, as_shr, sphgrid, fun2img, img2fun, fun2shr,
+                         fun2shc)
 from .geometry import hbar, bracket, norm_L2, inner_L2, norm_Linf, norm_L1, integral, qtime2seconds, seconds2qtime
 from .laplacian import (solve_poisson, laplace, PoissonHIP, solve_heat, solve_helmholtz, solve_viscdamp,
                         solve_globalqg, ViscDampStep)

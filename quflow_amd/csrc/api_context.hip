@@ -221,6 +221,9 @@ int qf_ctx_destroy(qf_ctx *ctx)
                     ctx->t32_partial, ctx->t32_arrive, ctx->W2, ctx->Whalf2, ctx->ns_inv, ctx->ns_tmp, ctx->multi_rowpart, ctx->scalars, ctx->sk_partial, ctx->sk_flags, ctx->basis, ctx->sh_stage, ctx->sh_omega};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    void *sht[] = {ctx->sht.omega, ctx->sht.tab, ctx->sht.col, ctx->sht.At, ctx->sht.tw, ctx->sht.f};
+    for (void *p : sht)
+        if (p) (void)hipFree(p);
     for (cplx *p : ctx->multi)
         if (p) (void)hipFree(p);
     for (int q = 0; q < 4; ++q) {

@@ -7,6 +7,8 @@
 #include <cstring>
 #include <limits>
 #include <chrono>
+#include <algorithm>
+#include <vector>
 
 #include "qf_api.h"
 
@@ -100,8 +102,10 @@ int qf_shr2mat(qf_ctx *ctx, const double *omega_host, long long n_omega, void *W
     const int Nmax = band_limit(ctx->N, n_omega);
     const long long ncopy = n_omega < NN ? n_omega : NN;
     // omega_host == NULL: the coefficients the last qf_mat2shr left on the device
-    if (omega_host)
+    if (omega_host) {
         QF_HIP(hipMemcpyAsync(ctx->sh_omega, omega_host, (size_t)ncopy * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        ctx->sh_shr_count = ncopy;
+    }
     cplx *dst = W_host ? ctx->stage : ctx->W;
     if (!W_host) ctx->w_skew_known = false;
     QF_TRY(qf_launch_shr2mat(ctx, Nmax, ctx->sh_omega, dst));
@@ -128,6 +132,7 @@ int qf_mat2shr(qf_ctx *ctx, const void *W_host, double *omega_host, long long n_
     }
     QF_HIP(hipMemsetAsync(ctx->sh_omega, 0, (size_t)ncopy * sizeof(double), ctx->stream));   // np.zeros, quantization.py:516
     QF_TRY(qf_launch_mat2shr(ctx, Nmax, src, ctx->sh_omega));
+    ctx->sh_shr_count = ncopy;
     // omega_host == NULL: leave the coefficients on the device (a following qf_shr2mat(NULL) uses them)
     if (omega_host)
         QF_HIP(hipMemcpyAsync(omega_host, ctx->sh_omega, (size_t)ncopy * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -147,6 +152,7 @@ int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host)
     }
     const size_t NN = (size_t)ctx->N * ctx->N;
     QF_HIP(hipMemcpyAsync(ctx->sh_omega, omega_host, NN * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+    ctx->sh_shr_count = 0;     // (complex now)
     cplx *dst = W_host ? ctx->stage : ctx->W;
     if (!W_host) ctx->w_skew_known = false;
     QF_TRY(qf_launch_shc2mat(ctx, ctx->sh_omega, dst));
@@ -170,9 +176,121 @@ int qf_mat2shc(qf_ctx *ctx, const void *W_host, void *omega_host)
         src = ctx->stage;
     }
     QF_TRY(qf_launch_mat2shc(ctx, src, ctx->sh_omega));
+    ctx->sh_shr_count = 0;
     QF_HIP(hipMemcpyAsync(omega_host, ctx->sh_omega, NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     return QF_OK;
+}
+
+// ---- spherical-harmonic synthesis (quflow/transforms.py:220-268, 422-438; kernels in sht.hip) ----------------
+static int sht_args(const char *who, long long n_omega, int L, const void *f_host)
+{
+    if (L < 1 || L > 8192) {
+        qf_set_error("%s: bandwidth L=%d is outside 1..8192", who, L);
+        return QF_ERR_INVALID;
+    }
+    if (n_omega < 1) {
+        qf_set_error("%s: empty coefficient array (n_omega=%lld)", who, n_omega);
+        return QF_ERR_INVALID;
+    }
+    if (!f_host) {
+        qf_set_error("%s: null output grid", who);
+        return QF_ERR_INVALID;
+    }
+    return QF_OK;
+}
+
+// ctx->sht grown to what (L, isreal) needs; a buffer that is too small is replaced (hipFree waits for the device)
+static int sht_reserve(qf_ctx *ctx, int L, int isreal)
+{
+    size_t want[6];
+    qf_sht_sizes(L, isreal, want);
+    qf_sht &S = ctx->sht;
+    void **bufs[6] = {(void **)&S.omega, (void **)&S.tab, (void **)&S.col, (void **)&S.At, (void **)&S.tw, (void **)&S.f};
+    for (int i = 0; i < 6; ++i) {
+        if (want[i] <= S.cap[i]) continue;
+        if (*bufs[i]) (void)hipFree(*bufs[i]);
+        *bufs[i] = nullptr;
+        S.cap[i] = 0;
+        QF_HIP(hipMalloc(bufs[i], want[i]));
+        S.cap[i] = want[i];
+    }
+    return QF_OK;
+}
+
+// The per-degree and per-order constants, in long double on the host (O(L)):
+//   tab[l]     = sqrt(4 pi) w_l,  w_l^2 = prod_{j=1..l} (L-j)/(L+j) -- berezin_multipliers(L) (utils.py:108-135, whose
+//                lgamma form is this product), or 1 without Berezin;
+//   tab[L + m] = lambda_mm(theta) / sin^m(theta) = (-1)^m sqrt((2m+1)/(4 pi) prod_{k=1..m} (2k-1)/(2k)).
+static int sht_tables(qf_ctx *ctx, int L, int berezin)
+{
+    std::vector<double> tab(2 * (size_t)L);
+    const long double fourpi = 4.0L * 3.141592653589793238462643383279502884L;
+    const long double rt4pi = std::sqrt(fourpi);
+    long double q = 1.0L;
+    for (int l = 0; l < L; ++l) {
+        if (l > 0) q *= (long double)(L - l) / (long double)(L + l);
+        tab[l] = (double)(berezin ? rt4pi * std::sqrt(q) : rt4pi);
+    }
+    long double prod = 1.0L;
+    for (int m = 0; m < L; ++m) {
+        if (m > 0) prod *= (long double)(2 * m - 1) / (long double)(2 * m);
+        const double v = (double)std::sqrt((long double)(2 * m + 1) / fourpi * prod);
+        tab[(size_t)L + m] = (m & 1) ? -v : v;
+    }
+    QF_HIP(hipMemcpyAsync(ctx->sht.tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));     // (tab is gone at return)
+    return QF_OK;
+}
+
+static int sht_run(qf_ctx *ctx, const void *omega_host, const double *omega_dev, long long n_valid, int L, int berezin, int shr,
+                   int isreal, void *f_host)
+{
+    QF_TRY(sht_reserve(ctx, L, isreal));
+    QF_TRY(sht_tables(ctx, L, berezin));
+    if (omega_host) {
+        QF_HIP(hipMemcpyAsync(ctx->sht.omega, omega_host, (size_t)n_valid * (shr ? sizeof(double) : sizeof(cplx)),
+                              hipMemcpyHostToDevice, ctx->stream));
+        omega_dev = ctx->sht.omega;
+    }
+    QF_TRY(qf_launch_sht_synth(ctx, L, shr, isreal, omega_dev, n_valid));
+    const size_t bytes = (size_t)L * (2 * (size_t)L - 1) * (isreal ? sizeof(double) : sizeof(cplx));
+    QF_HIP(hipMemcpyAsync(f_host, ctx->sht.f, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
+int qf_shr2fun(qf_ctx *ctx, const double *omega_host, long long n_omega, int L, int berezin, double *f_host)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(sht_args("qf_shr2fun", n_omega, L, f_host));
+    long long n = n_omega;
+    if (!omega_host) {
+        if (!ctx->sh_omega || ctx->sh_shr_count < 1) {
+            qf_set_error("qf_shr2fun: omega == NULL, but no qf_mat2shr has left real coefficients on this context");
+            return QF_ERR_STATE;
+        }
+        n = std::min(n, ctx->sh_shr_count);
+    }
+    // shr2shc (transforms.py:310-349) converts whole degrees only -- a last degree cut short stays zero -- and shc2fun
+    // then trims or pads to L^2: the entries below min(E^2, L^2), E^2 the largest square <= n, are used
+    long long e = (long long)std::sqrt((double)n);
+    while (e * e > n) --e;
+    while ((e + 1) * (e + 1) <= n) ++e;
+    n = std::min(e * e, (long long)L * L);
+    return sht_run(ctx, omega_host, ctx->sh_omega, n, L, berezin, 1, 1, f_host);
+}
+
+int qf_shc2fun(qf_ctx *ctx, const void *omega_host, long long n_omega, int L, int berezin, int isreal, void *f_host)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(sht_args("qf_shc2fun", n_omega, L, f_host));
+    if (!omega_host) {
+        qf_set_error("qf_shc2fun: null coefficient array");
+        return QF_ERR_INVALID;
+    }
+    const long long n = std::min(n_omega, (long long)L * L);
+    return sht_run(ctx, omega_host, nullptr, n, L, berezin, 0, isreal ? 1 : 0, f_host);
 }
 
 

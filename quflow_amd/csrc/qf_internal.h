@@ -266,6 +266,18 @@ struct qf_event_pair {
     int kernel_id;
 };
 
+// Scratch of the spherical-harmonic synthesis (sht.hip, qf_shr2fun / qf_shc2fun): allocated on first use, grown with the
+// bandwidth L (never shrunk), freed with the context.  `cap` holds the bytes each buffer has.
+struct qf_sht {
+    double *omega = nullptr;     // coefficients uploaded from the host (min(n_omega, L^2) entries, real or complex)
+    double *tab = nullptr;       // 2 L doubles: sqrt(4 pi) w_l, then the seeds lambda_mm / sin^m (host-made, long double)
+    cplx *col = nullptr;         // 2 x L(L+1)/2 complex: a_lm and (-1)^m a_l,-m as m-major columns (l contiguous)
+    double *At = nullptr;        // Kpad x ldA doubles: the Legendre stage's output, [k = 2m + (re, im)][ring]
+    double2 *tw = nullptr;       // 2L - 1 twiddles (cos, sin)(2 pi k / (2L - 1))
+    double *f = nullptr;         // the grid, (L, 2L-1) doubles or complex
+    size_t cap[6] = {0, 0, 0, 0, 0, 0};
+};
+
 struct qf_ctx {
     int N = 0;
     int device = 0;
@@ -331,6 +343,8 @@ struct qf_ctx {
     double *basis = nullptr;     // N(N+1)(2N+1)/6 doubles (quantization.py:68-113), uploaded once
     cplx *sh_stage = nullptr;    // 4 x N(N+1)/2 complex: packed coefficient / diagonal vectors
     double *sh_omega = nullptr;  // 2 N^2 doubles: omega on the device (real or complex)
+    long long sh_shr_count = 0;  // real coefficients sh_omega holds (the last qf_mat2shr / qf_shr2mat); 0: none
+    qf_sht sht;                  // spherical-harmonic synthesis scratch (sht.hip), grown with the bandwidth
 
     double *rowpart = nullptr;   // [tiles_n][N] partial row sums from the GEMM2 epilogue
     int rowpart_tiles = 0;
@@ -511,6 +525,12 @@ int qf_launch_shr2mat(qf_ctx *ctx, int Nmax, const double *omega_dev, cplx *W_de
 int qf_launch_mat2shr(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev);
 int qf_launch_shc2mat(qf_ctx *ctx, const double *omega_dev, cplx *W_dev);
 int qf_launch_mat2shc(qf_ctx *ctx, const cplx *W_dev, double *omega_dev);
+
+// ---- sht.hip: spherical-harmonic synthesis onto the MW grid at bandwidth L (scratch in ctx->sht, sized by the caller)
+// omega_dev: n_valid entries (real shr when shr != 0, else complex shc; entries past n_valid are zero); ctx->sht.tab
+// filled; result in ctx->sht.f: (L, 2L-1) doubles when isreal, complex128 otherwise.
+int qf_launch_sht_synth(qf_ctx *ctx, int L, int shr, int isreal, const double *omega_dev, long long n_valid);
+void qf_sht_sizes(int L, int isreal, size_t bytes[6]);   // what each ctx->sht buffer needs for (L, isreal)
 
 // ---- ozaki.hip: complex products on the int8 matrix cores from digit-sliced operands
 struct qf_oz_job {

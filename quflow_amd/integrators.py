@@ -960,6 +960,20 @@ class DeviceTrajectory:
         _lib.check(self._lib.qf_mat2shr(self.ctx.handle, None, ptr(omega), ctypes.c_longlong(n)))
         return omega
 
+    def fun(self, n_omega=None, berezin=True):
+        """shr2fun(self.shr(n_omega), berezin=berezin) (quflow/transforms.py:422-438) with the coefficients kept on the
+        device: only the (L, 2L-1) grid crosses PCIe, L = sqrt(n_omega).  n_omega = (N//2)**2 is the reference's 'funhalf'
+        output, berezin=False its 'funL2' (simulation.py:287-344)."""
+        from .transforms import _bandwidth
+        self._double_only("fun")
+        self._need_basis()
+        n = self.N * self.N if n_omega is None else int(n_omega)
+        L = _bandwidth(n, -1)
+        f = np.empty((L, 2 * L - 1), dtype=np.float64)
+        _lib.check(self._lib.qf_mat2shr(self.ctx.handle, None, None, ctypes.c_longlong(n)))
+        _lib.check(self._lib.qf_shr2fun(self.ctx.handle, None, ctypes.c_longlong(n), L, int(bool(berezin)), ptr(f)))
+        return f
+
     def download(self):
         W = np.zeros((self.N, self.N), dtype=self.dtype)
         _lib.check((self._lib.qf_c64_download_W if self.c64 else self._lib.qf_download_W)(self.ctx.handle, ptr(W)))

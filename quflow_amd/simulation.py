@@ -27,7 +27,8 @@ and only what the output needs comes down.  Restarting from `Simulation(filename
 bit-identically (tests/test_simulation.py:130-168: the stepper restarts its iteration vector at every
 chunk anyway, isospectral.py:430).
 
-Function-space outputs ('fun', 'funL2': transforms.py) are outside the scope of this package.
+Function-space outputs ('fun', 'funL2') are not written by Simulation; the synthesis itself is quflow_amd.transforms
+(shr2fun, DeviceTrajectory.fun).
 """
 import base64
 import datetime
