@@ -52,7 +52,7 @@ template <class S> double mach_eps(bool root)
     return root ? std::sqrt(e) : e;
 }
 
-// the launchers whose names differ between the precisions, overloaded on the element type
+// the two launchers that differ between the precisions (the table source, the kernel family), overloaded on the element type
 int launch_solve(qf_ctx *ctx, const cplx *W, cplx *P, double vareps, qf_guard g, const qf_decide *dec = nullptr)
 {
     return qf_launch_solve(ctx, ctx->poisson, W, P, vareps, 1, g, dec);
@@ -60,7 +60,7 @@ int launch_solve(qf_ctx *ctx, const cplx *W, cplx *P, double vareps, qf_guard g,
 // (the scale is applied in float32, as `Phalf *= vareps` on a complex64 array is: isospectral.py:488-492)
 int launch_solve(qf_ctx *ctx, const float2 *W, float2 *P, double vareps, qf_guard g)
 {
-    return qf_launch_solve_f32(ctx, ctx->c64->tab, W, P, (float)vareps, 1, g);
+    return qf_launch_solve(ctx, ctx->c64->tab, W, P, (float)vareps, 1, g);
 }
 int launch_gemm(qf_ctx *ctx, const cplx *A, const cplx *B, cplx *C, const qf_epilogue *ep, qf_guard g)
 {
@@ -70,23 +70,6 @@ int launch_gemm(qf_ctx *ctx, const float2 *A, const float2 *B, float2 *C, const 
 {
     return qf_launch_cgemm(ctx, A, B, C, ep, g);
 }
-int launch_update(qf_ctx *ctx, cplx *PW, cplx *W, cplx *dW_a, cplx *dW_b, cplx *Whalf, cplx *kahan_c, int reinitialize, qf_guard g)
-{
-    return qf_launch_update(ctx, PW, W, dW_a, dW_b, Whalf, kahan_c, reinitialize, g);
-}
-int launch_update(qf_ctx *ctx, float2 *PW, float2 *W, float2 *dW_a, float2 *dW_b, float2 *Whalf, float2 *kahan_c, int reinitialize,
-                  qf_guard g)
-{
-    return qf_launch_update_f32(ctx, PW, W, dW_a, dW_b, Whalf, kahan_c, reinitialize, g);
-}
-int launch_add(qf_ctx *ctx, const cplx *X, const cplx *Y, cplx *out) { return qf_launch_lincomb(ctx, 1.0, X, 1.0, Y, 0.0, out); }
-int launch_add(qf_ctx *ctx, const float2 *X, const float2 *Y, float2 *out) { return qf_launch_lincomb_f32(ctx, 1.0f, X, 1.0f, Y, out); }
-int launch_norm_inf(qf_ctx *ctx, const cplx *A, double *out) { return qf_launch_norm_inf(ctx, A, out); }
-int launch_norm_inf(qf_ctx *ctx, const float2 *A, double *out) { return qf_launch_norm_inf_f32(ctx, A, out); }
-int launch_skew_defect(qf_ctx *ctx, const cplx *A, double *out) { return qf_launch_skew_defect(ctx, A, out); }
-int launch_skew_defect(qf_ctx *ctx, const float2 *A, double *out) { return qf_launch_skew_defect_f32(ctx, A, out); }
-int launch_mirror_lower(qf_ctx *ctx, cplx *X) { return qf_launch_mirror_lower(ctx, X); }
-int launch_mirror_lower(qf_ctx *ctx, float2 *X) { return qf_launch_mirror_lower_f32(ctx, X); }
 
 // what the second product's epilogue reads and writes (kernel arguments: qf_epilogue / qf_epilogue_f); `fused`: also the
 // W pair and the next step's Whalf of the fused step end
@@ -119,7 +102,7 @@ template <class S> int check_skew(qf_ctx *ctx, S *w)
 {
     if (w->w_skew_known) return QF_OK;
     double defect = 0.0;
-    QF_TRY(launch_skew_defect(ctx, w->W, ctx->scalars + 4));
+    QF_TRY(qf_launch_skew_defect(ctx, w->W, ctx->scalars + 4));
     QF_TRY(read_scalar(ctx, ctx->scalars + 4, &defect));
     w->w_skew_known = (defect == 0.0);
     return QF_OK;
@@ -208,7 +191,7 @@ template <class S> int begin_increment(qf_ctx *ctx, S *w, bool carry)
     if (carry) {
         if (w->dw_cur != 0)
             QF_HIP(hipMemcpyAsync(w->dW[0], w->dW[w->dw_cur], mbytes, hipMemcpyDeviceToDevice, ctx->stream));
-        QF_TRY(launch_add(ctx, w->W, w->dW[0], w->Whalf));
+        QF_TRY(qf_launch_lincomb(ctx, 1, w->W, 1, w->dW[0], 0, w->Whalf));
     } else {
         QF_HIP(hipMemsetAsync(w->dW[0], 0, mbytes, ctx->stream));
         QF_HIP(hipMemcpyAsync(w->Whalf, w->W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
@@ -545,7 +528,7 @@ template <class S> int enqueue_step_end(qf_ctx *ctx, int step, int compsum, int 
     g.step = step;
     // W += 2*(PW - PW^H) (Kahan if compsum); Whalf = W + dW     isospectral.py:547-592
     prof_scope p(ctx, QF_KERNEL_UPDATE);
-    return launch_update(ctx, w->PW, w->W, w->dW[0], w->dW[1], w->Whalf, compsum ? w->kahan_c : nullptr, reinitialize, g);
+    return qf_launch_update(ctx, w->PW, w->W, w->dW[0], w->dW[1], w->Whalf, compsum ? w->kahan_c : nullptr, reinitialize, g);
 }
 
 // spin on the pinned record until `seq` advances have executed (the GPU is busy: no sleep)
@@ -628,7 +611,7 @@ template <class S> int fused_enter(qf_ctx *ctx, double dt, double tol, int minit
     rec->nonfinite = 0;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
     if (is_c64<S> || carry) {
-        if (tol_on_device) QF_TRY(launch_norm_inf(ctx, w->W, ctx->scalars));
+        if (tol_on_device) QF_TRY(qf_launch_norm_inf(ctx, w->W, ctx->scalars));
         QF_TRY(begin_increment(ctx, w, carry));
         QF_TRY(qf_launch_state_init(ctx, tol, minit, maxit, tol_on_device ? ctx->scalars : nullptr, tol_factor));
     } else {
@@ -655,8 +638,8 @@ template <class S> int fused_leave(qf_ctx *ctx, int steps, qf_isomp_stats *stats
     if (w_parity) std::swap(w->W, w->W2);             // the state ended in the second buffer of the pair
     if (wh_sel) std::swap(w->Whalf, w->Whalf2);       // keep "Whalf" = what the next iteration would read
     if (triangle_product(w) && steps > 0) {
-        QF_TRY(launch_mirror_lower(ctx, w->W));
-        QF_TRY(launch_mirror_lower(ctx, w->dW[w->dw_cur]));
+        QF_TRY(qf_launch_mirror_lower(ctx, w->W));
+        QF_TRY(qf_launch_mirror_lower(ctx, w->dW[w->dw_cur]));
     }
     if constexpr (!is_c64<S>)
         if (ctx->diag_at_exit) {
@@ -763,7 +746,7 @@ int isomp_impl(qf_ctx *ctx, double dt, int steps, double tol, int minit, int max
     // tolerance, isospectral.py:440-452
     if (tol < 0) {
         double nrm = 0.0;
-        QF_TRY(launch_norm_inf(ctx, w->W, ctx->scalars));
+        QF_TRY(qf_launch_norm_inf(ctx, w->W, ctx->scalars));
         QF_TRY(read_scalar(ctx, ctx->scalars, &nrm));
         tol = (mach_eps<S>(!compsum) * dt / hb) * nrm;
     }
@@ -1005,7 +988,7 @@ int c64_fixedpoint_products(const char *name, bool tri, qf_ctx *ctx, const void 
     // unguarded: parity 0, writes dW[1] (the triangle product: on and above the diagonal tiles)
     if (tri) {
         QF_TRY(qf_launch_cgemm_tri(ctx, f->PW, f->Phalf, &ep));
-        QF_TRY(qf_launch_mirror_lower_f32(ctx, f->dW[1]));
+        QF_TRY(qf_launch_mirror_lower(ctx, f->dW[1]));
         QF_TRY(qf_launch_sum_rowpart(ctx, f->rowpart, (N + qf_c64_tile(ctx) - 1) / qf_c64_tile(ctx), ctx->rowsum));
     } else {
         QF_TRY(qf_launch_cgemm(ctx, f->PW, f->Phalf, nullptr, &ep));

@@ -174,7 +174,7 @@ int qf_c64_laplacian_table(qf_ctx *ctx, int bc, float *lap_host)
     const size_t bytes = 2 * (size_t)ctx->N * ctx->N * sizeof(float);
     // (the resident table is the bc = True one: any other goes through the staging matrix, which has the same size)
     float *dst = bc ? f->lap : reinterpret_cast<float *>(f->stage);
-    if (!bc) QF_TRY(qf_launch_lap_table_f32(ctx, 0, dst));
+    if (!bc) QF_TRY(qf_launch_lap_table(ctx, 0, dst));
     QF_HIP(hipMemcpyAsync(lap_host, dst, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     return QF_OK;
@@ -190,7 +190,7 @@ int qf_c64_solve_poisson(qf_ctx *ctx, const void *W_host, void *P_host, int skew
     qf_c64 *f = ctx->c64;
     const size_t bytes = (size_t)ctx->N * ctx->N * sizeof(float2);
     QF_HIP(hipMemcpyAsync(f->stage, W_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    QF_TRY(qf_launch_solve_f32(ctx, f->tab, f->stage, f->Phalf, 1.0f, skewh));
+    QF_TRY(qf_launch_solve(ctx, f->tab, f->stage, f->Phalf, 1.0f, skewh));
     QF_HIP(hipMemcpyAsync(P_host, f->Phalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     return QF_OK;
@@ -210,9 +210,9 @@ int qf_c64_solve_tridiagonal(qf_ctx *ctx, const float *lap_host, const void *W_h
     float *lap_dev = reinterpret_cast<float *>(f->PW);
     float2 *tab_dev = f->dW[1];
     QF_HIP(hipMemcpyAsync(lap_dev, lap_host, 2 * NN * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    QF_TRY(qf_launch_build_factors_f32(ctx, lap_dev, tab_dev));
+    QF_TRY(qf_launch_build_factors(ctx, lap_dev, tab_dev));
     QF_HIP(hipMemcpyAsync(f->stage, W_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    QF_TRY(qf_launch_solve_f32(ctx, tab_dev, f->stage, f->Phalf, 1.0f, skewh));
+    QF_TRY(qf_launch_solve(ctx, tab_dev, f->stage, f->Phalf, 1.0f, skewh));
     QF_HIP(hipMemcpyAsync(P_host, f->Phalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     f->increment_valid = false;      // (dW[1] was scratch)
@@ -229,7 +229,7 @@ int qf_c64_laplace(qf_ctx *ctx, const void *P_host, void *W_host)
     qf_c64 *f = ctx->c64;
     const size_t bytes = (size_t)ctx->N * ctx->N * sizeof(float2);
     QF_HIP(hipMemcpyAsync(f->stage, P_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    QF_TRY(qf_launch_laplace_f32(ctx, f->stage, f->Phalf));
+    QF_TRY(qf_launch_laplace(ctx, f->stage, f->Phalf));
     QF_HIP(hipMemcpyAsync(W_host, f->Phalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     return QF_OK;
@@ -242,8 +242,8 @@ int qf_c64_diagnostics(qf_ctx *ctx, double *energy_euler, double *enstrophy)
     qf_c64 *f = ctx->c64;
     const int N = ctx->N;
     // P = solve_poisson(W); energy = -inner_L2(W, P)/2; enstrophy = inner_L2(W, W)/2  (physics.py:26-38)
-    QF_TRY(qf_launch_solve_f32(ctx, f->tab, f->W, f->stage, 1.0f, 1));
-    QF_TRY(qf_launch_inner2_f32(ctx, f->W, f->stage, ctx->scalars + 2));
+    QF_TRY(qf_launch_solve(ctx, f->tab, f->W, f->stage, 1.0f, 1));
+    QF_TRY(qf_launch_inner2(ctx, f->W, f->stage, ctx->scalars + 2));
     QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 2, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     const double wp = ctx->host_scalars[0], ww = ctx->host_scalars[1];

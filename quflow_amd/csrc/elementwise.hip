@@ -2,6 +2,8 @@
 // the end-of-step update W += 2 (PW - PW^H) (isospectral.py:547-592, with the Kahan
 // variant :553-586), the residual / tolerance norms (isospectral.py:448,534) and the
 // diagnostics reductions (quflow/physics.py:26-38, quflow/geometry.py:72-76).
+// The passes the complex64 stepper shares are templates on the element type C (cplx or float2): elementwise
+// arithmetic in C's real type, as the reference's complex64 arrays compute; reductions in double either way.
 #include "qf_internal.h"
 
 #pragma clang fp contract(off)  // Kahan summation must not be re-associated or fused
@@ -9,6 +11,15 @@
 namespace {
 
 constexpr int TU = 32;  // update tile
+
+// the complex element types' differences: building one; |z| and Re(a conj(b)) formed in the entries' precision and
+// handed to a double reduction
+__device__ __forceinline__ cplx make_c(double re, double im) { return make_double2(re, im); }
+__device__ __forceinline__ float2 make_c(float re, float im) { return make_float2(re, im); }
+__device__ __forceinline__ double modulus_d(cplx z) { return hypot(z.x, z.y); }
+__device__ __forceinline__ double modulus_d(float2 z) { return (double)hypotf(z.x, z.y); }
+__device__ __forceinline__ double re_dot_d(cplx a, cplx b) { return a.x * b.x + a.y * b.y; }
+__device__ __forceinline__ double re_dot_d(float2 a, float2 b) { return (double)(a.x * b.x + a.y * b.y); }
 
 // End-of-step bookkeeping, executed by the LAST block of k_update to finish (ticket counter), i.e.
 // after every block has read the control state: advance the step counter, reset the per-step
@@ -43,25 +54,26 @@ __device__ void qf_step_advance(qf_dev_state *state, qf_host_record *rec, const 
 // W += 2 * (PW - PW^H);  Whalf = W + dW  (dW == nullptr: Whalf = W).
 // Tile (bi,bj) reads PW tiles (bi,bj) and (bj,bi); the mirrored one goes through LDS so that
 // both global reads are row-coalesced.
-template <bool KAHAN>
-__global__ __launch_bounds__(256) void k_update(int N, const cplx *__restrict__ PW, cplx *__restrict__ W,
-                                                 cplx *dW_a, cplx *dW_b, cplx *__restrict__ Whalf,
-                                                 cplx *__restrict__ kc, int reinitialize, qf_guard guard,
+template <class C, bool KAHAN>
+__global__ __launch_bounds__(256) void k_update(int N, const C *__restrict__ PW, C *__restrict__ W,
+                                                 C *dW_a, C *dW_b, C *__restrict__ Whalf,
+                                                 C *__restrict__ kc, int reinitialize, qf_guard guard,
                                                  qf_dev_state *state, qf_host_record *rec, unsigned *ticket)
 {
+    using R = typename C::value_type;
     // the update runs once the iteration of step `guard.step` has finished (break taken or
     // maxit reached); otherwise the launch only takes part in the end-of-step ticket
     const bool due = qf_guard_step_end(guard);
     if (due) {
     // current iteration vector: the device knows how many iterations were executed
-    cplx *dWc = (guard.state && guard.state->dw_parity) ? dW_b : dW_a;
-    const cplx *dW = reinitialize ? nullptr : dWc;
-    __shared__ cplx Ts[TU][TU + 1];
+    C *dWc = (guard.state && guard.state->dw_parity) ? dW_b : dW_a;
+    const C *dW = reinitialize ? nullptr : dWc;
+    __shared__ C Ts[TU][TU + 1];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
     const int i0 = blockIdx.y * TU, j0 = blockIdx.x * TU;
     for (int r = ty; r < TU; r += 8) {
         int gj = j0 + r, gi = i0 + tx;  // row gj of the mirrored tile, column gi
-        cplx tv = make_double2(0.0, 0.0);
+        C tv = make_c(R(0), R(0));
         if (gj < N && gi < N) tv = PW[(size_t)gj * N + gi];
         Ts[r][tx] = tv;
     }
@@ -70,17 +82,17 @@ __global__ __launch_bounds__(256) void k_update(int N, const cplx *__restrict__ 
         int gi = i0 + r, gj = j0 + tx;
         if (gi < N && gj < N) {
             const size_t e = (size_t)gi * N + gj;
-            const cplx pw = PW[e];
-            const cplx pwt = Ts[tx][r];
+            const C pw = PW[e];
+            const C pwt = Ts[tx][r];
             // 2 * (PW[i,j] - conj(PW[j,i]))   (conj_subtract_ then `PWcomm *= 2`, isospectral.py:503,547)
-            const double dr = 2.0 * (pw.x - pwt.x);
-            const double di = 2.0 * (pw.y + pwt.y);
-            cplx w = W[e];
+            const R dr = R(2) * (pw.x - pwt.x);
+            const R di = R(2) * (pw.y + pwt.y);
+            C w = W[e];
             if (KAHAN) {
                 // isospectral.py:568-586:  y = d - c;  t = W + y;  c = (t - W) - y;  W = t
-                cplx c = kc[e];
-                const double yr = dr - c.x, yi = di - c.y;
-                const double tr = w.x + yr, ti = w.y + yi;
+                C c = kc[e];
+                const R yr = dr - c.x, yi = di - c.y;
+                const R tr = w.x + yr, ti = w.y + yi;
                 c.x = (tr - w.x) - yr;
                 c.y = (ti - w.y) - yi;
                 kc[e] = c;
@@ -92,11 +104,11 @@ __global__ __launch_bounds__(256) void k_update(int N, const cplx *__restrict__ 
             }
             W[e] = w;
             if (dW) {
-                const cplx d = dW[e];
-                Whalf[e] = make_double2(w.x + d.x, w.y + d.y);  // isospectral.py:481-482 of the next step
+                const C d = dW[e];
+                Whalf[e] = make_c(w.x + d.x, w.y + d.y);        // isospectral.py:481-482 of the next step
             } else {
                 Whalf[e] = w;
-                dWc[e] = make_double2(0.0, 0.0);                // dW.fill(0), isospectral.py:471-472
+                dWc[e] = make_c(R(0), R(0));                    // dW.fill(0), isospectral.py:471-472
             }
         }
     }
@@ -177,21 +189,24 @@ __global__ __launch_bounds__(256) void k_erk_stage(int N, const cplx *__restrict
 }
 
 // out = a*X + b*Y + c*I  (Y may be nullptr; out may alias X or Y): the O(N^2) glue of the
-// Newton-Schulz linear solves of isomp_simple / isomp_quasinewton (api_steppers.hip)
-__global__ __launch_bounds__(256) void k_lincomb(int N, double a, const cplx *X, double b, const cplx *Y, double c,
-                                                  cplx *out)
+// Newton-Schulz linear solves of isomp_simple / isomp_quasinewton (api_steppers.hip) and
+// Whalf = W + dW of a carried increment (api_isomp.hip)
+template <class C>
+__global__ __launch_bounds__(256) void k_lincomb(int N, typename C::value_type a, const C *X, typename C::value_type b,
+                                                  const C *Y, typename C::value_type c, C *out)
 {
+    using R = typename C::value_type;
     const size_t n = (size_t)N * N;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const cplx x = X[e];
-        double re = a * x.x, im = a * x.y;
+        const C x = X[e];
+        R re = a * x.x, im = a * x.y;
         if (Y) {
-            const cplx y = Y[e];
+            const C y = Y[e];
             re += b * y.x;
             im += b * y.y;
         }
-        if (c != 0.0 && e % ((size_t)N + 1) == 0) re += c;
-        out[e] = make_double2(re, im);
+        if (c != R(0) && e % ((size_t)N + 1) == 0) re += c;
+        out[e] = make_c(re, im);
     }
 }
 
@@ -220,16 +235,18 @@ __global__ __launch_bounds__(256) void k_neg_conj_transpose(int N, const cplx *_
 // X[j,i] = -conj(X[i,j]) for i < j: restores the lower triangle of a skew-Hermitian matrix from its
 // upper one (the fused upper-triangle second product leaves W and dW above the diagonal only,
 // zgemm.hip).  One block per 32 x 32 tile strictly below the diagonal, both accesses row-coalesced.
-__global__ __launch_bounds__(256) void k_mirror_lower(int N, cplx *__restrict__ X)
+template <class C>
+__global__ __launch_bounds__(256) void k_mirror_lower(int N, C *__restrict__ X)
 {
-    __shared__ cplx Ts[TU][TU + 1];
+    using R = typename C::value_type;
+    __shared__ C Ts[TU][TU + 1];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int bi = blockIdx.y, bj = blockIdx.x;    // target tile (rows bi, columns bj)
     if (bj > bi) return;
     const int i0 = bi * TU, j0 = bj * TU;
     for (int r = ty; r < TU; r += 8) {
         const int gj = j0 + r, gi = i0 + tx;       // source: row gj, column gi (above the diagonal when gj < gi)
-        cplx tv = make_double2(0.0, 0.0);
+        C tv = make_c(R(0), R(0));
         if (gj < N && gi < N) tv = X[(size_t)gj * N + gi];
         Ts[r][tx] = tv;
     }
@@ -237,8 +254,8 @@ __global__ __launch_bounds__(256) void k_mirror_lower(int N, cplx *__restrict__ 
     for (int r = ty; r < TU; r += 8) {
         const int gi = i0 + r, gj = j0 + tx;
         if (gi < N && gj < N && gj < gi) {
-            const cplx t = Ts[tx][r];
-            X[(size_t)gi * N + gj] = make_double2(-t.x, t.y);
+            const C t = Ts[tx][r];
+            X[(size_t)gi * N + gj] = make_c(-t.x, t.y);
         }
     }
 }
@@ -343,14 +360,15 @@ __device__ __forceinline__ double wave_max(double v)
 }
 
 // rowsum[i] = sum_j |A[i,j]|, one 256-thread block per row (fixed reduction tree)
-__global__ __launch_bounds__(256) void k_row_abs_sum(int N, const cplx *__restrict__ A, double *__restrict__ rowsum)
+template <class C>
+__global__ __launch_bounds__(256) void k_row_abs_sum(int N, const C *__restrict__ A, double *__restrict__ rowsum)
 {
     __shared__ double part[4];
     const int i = blockIdx.x;
     double s = 0.0;
     for (int j = threadIdx.x; j < N; j += 256) {
-        cplx z = A[(size_t)i * N + j];
-        s += hypot(z.x, z.y);
+        C z = A[(size_t)i * N + j];
+        s += modulus_d(z);
     }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
@@ -391,20 +409,23 @@ __global__ __launch_bounds__(1024) void k_max_rows(int N, int tiles, const doubl
 
 // max |A[i,j] + conj(A[j,i])| and max |A[i,j]| over the rows of one block (NaN-propagating:
 // a NaN anywhere makes the defect NaN, which fails the host's `<=` test).
-__global__ __launch_bounds__(256) void k_skew_defect_partial(int N, const cplx *__restrict__ A,
+// (the sums in C's real type, as A + A^H of the reference's arrays)
+template <class C>
+__global__ __launch_bounds__(256) void k_skew_defect_partial(int N, const C *__restrict__ A,
                                                               double *__restrict__ defect, double *__restrict__ amax)
 {
+    using R = typename C::value_type;
     __shared__ double sd[4], sa[4];
     double d = 0.0, a = 0.0;
     bool nan = false;
     for (int i = blockIdx.x; i < N; i += gridDim.x)
         for (int j = threadIdx.x; j < N; j += 256) {
-            const cplx x = A[(size_t)i * N + j], y = A[(size_t)j * N + i];
-            const double dr = x.x + y.x, di = x.y - y.y;
-            const double dd = fmax(fabs(dr), fabs(di));
+            const C x = A[(size_t)i * N + j], y = A[(size_t)j * N + i];
+            const R dr = x.x + y.x, di = x.y - y.y;
+            const double dd = fmax(fabs((double)dr), fabs((double)di));
             if (dd != dd) nan = true;
             d = fmax(d, dd);
-            a = fmax(a, fmax(fabs(x.x), fabs(x.y)));
+            a = fmax(a, fmax(fabs((double)x.x), fabs((double)x.y)));
         }
     if (nan) d = __builtin_inf();
     d = wave_max(d);
@@ -660,20 +681,22 @@ __global__ __launch_bounds__(64) void k_sum_partials(int n, const double *__rest
 
 // both inner products of the diagnostics in one pass (quflow/physics.py:26-38): partial sums exactly as
 // k_inner_partial forms them, folded by the block that finishes last exactly as k_sum_partials does
-__global__ __launch_bounds__(256) void k_inner2(size_t n, const cplx *__restrict__ A, const cplx *__restrict__ B,
+template <class C>
+__global__ __launch_bounds__(256) void k_inner2(size_t n, const C *__restrict__ A, const C *__restrict__ B,
                                                  double *__restrict__ partial, unsigned *ticket, double *__restrict__ out)
 {
+    using R = typename C::value_type;
     __shared__ double pab[4], paa[4];
     __shared__ int last;
     double sab = 0.0, saa = 0.0;
     // four strides' loads in flight per thread, added in the order of the plain loop (same bits)
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t e0 = (size_t)blockIdx.x * 256 + threadIdx.x; e0 < n; e0 += 4 * stride) {
-        cplx a[4], b[4];
+        C a[4], b[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const size_t e = e0 + u * stride;
-            a[u] = b[u] = make_double2(0.0, 0.0);
+            a[u] = b[u] = make_c(R(0), R(0));
             if (e < n) {
                 a[u] = A[e];
                 b[u] = B[e];
@@ -682,8 +705,8 @@ __global__ __launch_bounds__(256) void k_inner2(size_t n, const cplx *__restrict
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (e0 + u * stride < n) {
-                sab += a[u].x * b[u].x + a[u].y * b[u].y;
-                saa += a[u].x * a[u].x + a[u].y * a[u].y;
+                sab += re_dot_d(a[u], b[u]);
+                saa += re_dot_d(a[u], a[u]);
             }
         }
     }
@@ -724,27 +747,28 @@ int qf_launch_call_begin(qf_ctx *ctx, double tol, int minit, int maxit, int auto
     return QF_OK;
 }
 
-int qf_launch_inner2(qf_ctx *ctx, const cplx *A, const cplx *B, double *out_dev)
+template <class C> int qf_launch_inner2(qf_ctx *ctx, const C *A, const C *B, double *out_dev)
 {
     const size_t n = (size_t)ctx->N * ctx->N;
     int blocks = (int)((n + 255) / 256);
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(k_inner2, dim3(blocks), dim3(256), 0, ctx->stream, n, A, B, ctx->scalars + 64, ctx->ticket + 640, out_dev);
+    hipLaunchKernelGGL(k_inner2<C>, dim3(blocks), dim3(256), 0, ctx->stream, n, A, B, ctx->scalars + 64, ctx->ticket + 640, out_dev);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }
 
-int qf_launch_update(qf_ctx *ctx, const cplx *PW, cplx *W, const cplx *dW_a, const cplx *dW_b, cplx *Whalf,
-                     cplx *kahan_c, int reinitialize, qf_guard guard)
+template <class C>
+int qf_launch_update(qf_ctx *ctx, const C *PW, C *W, const C *dW_a, const C *dW_b, C *Whalf, qf_same<C> *kahan_c,
+                     int reinitialize, qf_guard guard)
 {
     const int N = ctx->N;
     dim3 grid((N + TU - 1) / TU, (N + TU - 1) / TU), block(256);
-    cplx *a = const_cast<cplx *>(dW_a), *b = const_cast<cplx *>(dW_b);
+    C *a = const_cast<C *>(dW_a), *b = const_cast<C *>(dW_b);
     if (kahan_c)
-        hipLaunchKernelGGL(k_update<true>, grid, block, 0, ctx->stream, N, PW, W, a, b, Whalf, kahan_c, reinitialize, guard,
+        hipLaunchKernelGGL((k_update<C, true>), grid, block, 0, ctx->stream, N, PW, W, a, b, Whalf, kahan_c, reinitialize, guard,
                            guard.state ? ctx->state : nullptr, ctx->host_rec, ctx->ticket);
     else
-        hipLaunchKernelGGL(k_update<false>, grid, block, 0, ctx->stream, N, PW, W, a, b, Whalf, kahan_c, reinitialize, guard,
+        hipLaunchKernelGGL((k_update<C, false>), grid, block, 0, ctx->stream, N, PW, W, a, b, Whalf, kahan_c, reinitialize, guard,
                            guard.state ? ctx->state : nullptr, ctx->host_rec, ctx->ticket);
     QF_HIP(hipGetLastError());
     return QF_OK;
@@ -772,9 +796,9 @@ int qf_launch_norm_from_rowpart(qf_ctx *ctx, const double *rowpart, int tiles, d
     return QF_OK;
 }
 
-int qf_launch_norm_inf(qf_ctx *ctx, const cplx *A, double *out_dev)
+template <class C> int qf_launch_norm_inf(qf_ctx *ctx, const C *A, double *out_dev)
 {
-    hipLaunchKernelGGL(k_row_abs_sum, dim3(ctx->N), dim3(256), 0, ctx->stream, ctx->N, A, ctx->rowsum);
+    hipLaunchKernelGGL(k_row_abs_sum<C>, dim3(ctx->N), dim3(256), 0, ctx->stream, ctx->N, A, ctx->rowsum);
     QF_HIP(hipGetLastError());
     return qf_launch_norm_from_rowpart(ctx, ctx->rowsum, 1, out_dev);
 }
@@ -809,20 +833,22 @@ int qf_launch_magnetic_update(qf_ctx *ctx, const cplx *BT, cplx *W, const cplx *
     return QF_OK;
 }
 
-int qf_launch_lincomb(qf_ctx *ctx, double a, const cplx *X, double b, const cplx *Y, double c, cplx *out)
+template <class C>
+int qf_launch_lincomb(qf_ctx *ctx, double a, const C *X, double b, const qf_same<C> *Y, double c, C *out)
 {
+    using R = typename C::value_type;
     const size_t n = (size_t)ctx->N * ctx->N;
     int blocks = (int)((n + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_lincomb, dim3(blocks), dim3(256), 0, ctx->stream, ctx->N, a, X, b, Y, c, out);
+    hipLaunchKernelGGL(k_lincomb<C>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->N, (R)a, X, (R)b, Y, (R)c, out);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }
 
-int qf_launch_mirror_lower(qf_ctx *ctx, cplx *X)
+template <class C> int qf_launch_mirror_lower(qf_ctx *ctx, C *X)
 {
     const int tiles = (ctx->N + TU - 1) / TU;
-    hipLaunchKernelGGL(k_mirror_lower, dim3(tiles, tiles), dim3(256), 0, ctx->stream, ctx->N, X);
+    hipLaunchKernelGGL(k_mirror_lower<C>, dim3(tiles, tiles), dim3(256), 0, ctx->stream, ctx->N, X);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }
@@ -844,17 +870,31 @@ int qf_launch_sum_rowpart(qf_ctx *ctx, const double *rowpart, int tiles, double 
     return QF_OK;
 }
 
-int qf_launch_skew_defect(qf_ctx *ctx, const cplx *A, double *out_dev)
+template <class C> int qf_launch_skew_defect(qf_ctx *ctx, const C *A, double *out_dev)
 {
     const int N = ctx->N;
     int blocks = N < 1024 ? N : 1024;
     double *partial = ctx->scalars + 64;   // [2][blocks]
-    hipLaunchKernelGGL(k_skew_defect_partial, dim3(blocks), dim3(256), 0, ctx->stream, N, A, partial, partial + 1024);
+    hipLaunchKernelGGL(k_skew_defect_partial<C>, dim3(blocks), dim3(256), 0, ctx->stream, N, A, partial, partial + 1024);
     QF_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_max_partials2, dim3(1), dim3(64), 0, ctx->stream, blocks, partial, partial + 1024, out_dev);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }
+
+// complex128 and complex64 instances (the launch geometry does not depend on the element type)
+template int qf_launch_update(qf_ctx *, const cplx *, cplx *, const cplx *, const cplx *, cplx *, cplx *, int, qf_guard);
+template int qf_launch_update(qf_ctx *, const float2 *, float2 *, const float2 *, const float2 *, float2 *, float2 *, int, qf_guard);
+template int qf_launch_mirror_lower(qf_ctx *, cplx *);
+template int qf_launch_mirror_lower(qf_ctx *, float2 *);
+template int qf_launch_norm_inf(qf_ctx *, const cplx *, double *);
+template int qf_launch_norm_inf(qf_ctx *, const float2 *, double *);
+template int qf_launch_inner2(qf_ctx *, const cplx *, const cplx *, double *);
+template int qf_launch_inner2(qf_ctx *, const float2 *, const float2 *, double *);
+template int qf_launch_skew_defect(qf_ctx *, const cplx *, double *);
+template int qf_launch_skew_defect(qf_ctx *, const float2 *, double *);
+template int qf_launch_lincomb(qf_ctx *, double, const cplx *, double, const cplx *, double, cplx *);
+template int qf_launch_lincomb(qf_ctx *, double, const float2 *, double, const float2 *, double, float2 *);
 
 int qf_launch_inner(qf_ctx *ctx, const cplx *A, const cplx *B, double *out_dev)
 {

@@ -967,7 +967,7 @@ int qf_launch_laplace(qf_ctx *ctx, const cplx *P, cplx *W)
 }
 
 // ---- complex64 data: float32 tables, float32 arithmetic (cpu.py:725) ----
-int qf_launch_lap_table_f32(qf_ctx *ctx, int bc, float *lap_dev)
+int qf_launch_lap_table(qf_ctx *ctx, int bc, float *lap_dev)
 {
     size_t NN = (size_t)ctx->N * ctx->N;
     int threads = 256;
@@ -977,7 +977,7 @@ int qf_launch_lap_table_f32(qf_ctx *ctx, int bc, float *lap_dev)
     return QF_OK;
 }
 
-int qf_launch_build_factors_f32(qf_ctx *ctx, const float *lap_dev, float2 *tab)
+int qf_launch_build_factors(qf_ctx *ctx, const float *lap_dev, float2 *tab)
 {
     int threads = 64;
     unsigned blocks = (unsigned)((ctx->N + 1 + threads - 1) / threads);
@@ -986,12 +986,12 @@ int qf_launch_build_factors_f32(qf_ctx *ctx, const float *lap_dev, float2 *tab)
     return QF_OK;
 }
 
-int qf_launch_solve_f32(qf_ctx *ctx, const float2 *tab, const float2 *W, float2 *P, float scale, int skewh, qf_guard guard)
+int qf_launch_solve(qf_ctx *ctx, const float2 *tab, const float2 *W, float2 *P, float scale, int skewh, qf_guard guard)
 {
     return launch_solve<float>(ctx, tab, W, P, scale, skewh, guard, nullptr);
 }
 
-int qf_launch_laplace_f32(qf_ctx *ctx, const float2 *P, float2 *W)
+int qf_launch_laplace(qf_ctx *ctx, const float2 *P, float2 *W)
 {
     const int N = ctx->N;
     dim3 block(256), grid((N + 255) / 256, N);

@@ -433,13 +433,14 @@ int qf_launch_solve(qf_ctx *ctx, const qf_factors &f, const cplx *W, cplx *P, do
 int qf_launch_decide(qf_ctx *ctx, const qf_decide &dec);      // the deferred decision alone (end of a call)
 int qf_launch_laplace(qf_ctx *ctx, const cplx *P, cplx *W);
 
-int qf_launch_lap_table_f32(qf_ctx *ctx, int bc, float *lap_dev);
-int qf_launch_build_factors_f32(qf_ctx *ctx, const float *lap_dev, float2 *tab);
-int qf_launch_solve_f32(qf_ctx *ctx, const float2 *tab, const float2 *W, float2 *P, float scale, int skewh,
-                        qf_guard guard = qf_guard());
-int qf_launch_laplace_f32(qf_ctx *ctx, const float2 *P, float2 *W);
+// complex64 data: float32 tables, float32 arithmetic (quflow/laplacian/cpu.py:725)
+int qf_launch_lap_table(qf_ctx *ctx, int bc, float *lap_dev);
+int qf_launch_build_factors(qf_ctx *ctx, const float *lap_dev, float2 *tab);
+int qf_launch_solve(qf_ctx *ctx, const float2 *tab, const float2 *W, float2 *P, float scale, int skewh,
+                    qf_guard guard = qf_guard());
+int qf_launch_laplace(qf_ctx *ctx, const float2 *P, float2 *W);
 
-// ---- single.hip: complex64 products and elementwise passes
+// ---- single.hip: complex64 products
 int qf_c64_alloc(qf_ctx *ctx);
 void qf_c64_free(qf_c64 *f);
 int qf_launch_cgemm(qf_ctx *ctx, const float2 *A, const float2 *B, float2 *C, const qf_epilogue_f *ep, qf_guard guard = qf_guard());
@@ -450,13 +451,6 @@ int qf_c64_tile_first(const qf_ctx *ctx);
 // the second product on the upper triangle of 64x64 tiles (requires N % 64 == 0 and qf_c64_tri_alloc)
 int qf_c64_tri_alloc(qf_ctx *ctx);
 int qf_launch_cgemm_tri(qf_ctx *ctx, const float2 *A, const float2 *B, const qf_epilogue_f *ep, qf_guard guard = qf_guard());
-int qf_launch_mirror_lower_f32(qf_ctx *ctx, float2 *X);
-int qf_launch_update_f32(qf_ctx *ctx, const float2 *PW, float2 *W, float2 *dW_a, float2 *dW_b, float2 *Whalf, float2 *kahan_c,
-                         int reinitialize, qf_guard guard = qf_guard());
-int qf_launch_norm_inf_f32(qf_ctx *ctx, const float2 *A, double *out_dev);
-int qf_launch_inner2_f32(qf_ctx *ctx, const float2 *A, const float2 *B, double *out_dev);
-int qf_launch_skew_defect_f32(qf_ctx *ctx, const float2 *A, double *out_dev);
-int qf_launch_lincomb_f32(qf_ctx *ctx, float a, const float2 *X, float b, const float2 *Y, float2 *out);
 
 // ---- zgemm.hip
 struct qf_epilogue {
@@ -562,10 +556,16 @@ int qf_launch_oz_gemm(qf_ctx *ctx, const signed char *pa, const double *sa, cons
                       const double *diag = nullptr);
 
 // ---- elementwise.hip
+// The launchers templated on the element type C are instantiated for cplx (complex128) and float2 (complex64): arithmetic
+// in C's real type, reductions in double.  An optional argument is typed qf_same<C> *: C is deduced from the others
+// alone, so that a plain nullptr may stand there.
+template <class T> struct qf_same_type { typedef T type; };
+template <class T> using qf_same = typename qf_same_type<T>::type;
 // W += 2(PW - PW^H) at the end of a step.  dW_a/dW_b: the ping-pong pair; the kernel picks the
 // current one from the parity of the executed iteration count (device state) when guarded.
-int qf_launch_update(qf_ctx *ctx, const cplx *PW, cplx *W, const cplx *dW_a, const cplx *dW_b, cplx *Whalf,
-                     cplx *kahan_c, int reinitialize, qf_guard guard = qf_guard());
+template <class C>
+int qf_launch_update(qf_ctx *ctx, const C *PW, C *W, const C *dW_a, const C *dW_b, C *Whalf, qf_same<C> *kahan_c,
+                     int reinitialize, qf_guard guard = qf_guard());
 int qf_launch_debug_modulus(qf_ctx *ctx, int n, const double *er, const double *ei, double *out_mod, double *out_sqrt);
 int qf_launch_norm_from_rowpart(qf_ctx *ctx, const double *rowpart, int tiles, double *out_dev);
 // residual norm + exit decision of iteration `guard.iter` (isospectral.py:523-536), on device
@@ -573,11 +573,11 @@ int qf_launch_norm_decide(qf_ctx *ctx, const double *rowpart, int tiles, qf_guar
 // norm_dev != nullptr: automatic tolerance tol = tol_factor * (*norm_dev), formed on the device
 // (isospectral.py:440-448: (mach_eps*dt/hb) * |W|_inf) so that the host never waits for the norm
 int qf_launch_state_init(qf_ctx *ctx, double tol, int minit, int maxit, const double *norm_dev = nullptr, double tol_factor = 0.0);
-int qf_launch_norm_inf(qf_ctx *ctx, const cplx *A, double *out_dev);
+template <class C> int qf_launch_norm_inf(qf_ctx *ctx, const C *A, double *out_dev);
 // entry of a fused-protocol call in one launch: dW[0] = 0, Whalf = W, |W|_inf -> tolerance (auto_tol), control state reset
 int qf_launch_call_begin(qf_ctx *ctx, double tol, int minit, int maxit, int auto_tol, double tol_factor);
 // out_dev[0] = sum Re(A conj(B)), out_dev[1] = sum |A|^2 in one pass
-int qf_launch_inner2(qf_ctx *ctx, const cplx *A, const cplx *B, double *out_dev);
+template <class C> int qf_launch_inner2(qf_ctx *ctx, const C *A, const C *B, double *out_dev);
 int qf_launch_inner(qf_ctx *ctx, const cplx *A, const cplx *B, double *out_dev);  // sum Re(A conj(B))
 // explicit Runge-Kutta stage on the products A = P@X, B = X@P (B == nullptr: B = A^H, skew-Hermitian case)
 int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, double inv_hb, const cplx *W, cplx *acc,
@@ -586,9 +586,10 @@ int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, double inv_hb
 int qf_launch_magnetic_fix(qf_ctx *ctx, const cplx *BTP, const cplx *BT, cplx *dW, const cplx *dW_old, const cplx *W,
                            cplx *Whalf, double *rowpart);
 int qf_launch_magnetic_update(qf_ctx *ctx, const cplx *BT, cplx *W, const cplx *dW, cplx *Whalf);
-int qf_launch_lincomb(qf_ctx *ctx, double a, const cplx *X, double b, const cplx *Y, double c, cplx *out);  // a X + b Y + c I
+template <class C>
+int qf_launch_lincomb(qf_ctx *ctx, double a, const C *X, double b, const qf_same<C> *Y, double c, C *out);   // a X + b Y + c I
 int qf_launch_neg_conj_transpose(qf_ctx *ctx, const cplx *X, cplx *out);                                       // -X^H
-int qf_launch_mirror_lower(qf_ctx *ctx, cplx *X);                                                              // X[j,i] = -conj(X[i,j]), i < j
+template <class C> int qf_launch_mirror_lower(qf_ctx *ctx, C *X);                                               // X[j,i] = -conj(X[i,j]), i < j
 int qf_launch_sum_rowpart(qf_ctx *ctx, const double *rowpart, int tiles, double *rowsum_dev);
 // out_dev[0] = max_ij |A[i,j] + conj(A[j,i])|, out_dev[1] = max_ij |A[i,j]|
-int qf_launch_skew_defect(qf_ctx *ctx, const cplx *A, double *out_dev);
+template <class C> int qf_launch_skew_defect(qf_ctx *ctx, const C *A, double *out_dev);

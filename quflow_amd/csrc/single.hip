@@ -4,23 +4,22 @@
 // float32 Thomas solve (quflow/laplacian/cpu.py:725, `dtype=type(W[0,0].real)`), complex64 np.matmul for the two
 // products (quflow/integrators/isospectral.py:496,499), complex64 elementwise passes, and the automatic tolerance
 // from the float32 machine epsilon (isospectral.py:440-448).  This file holds the float32 kernels that are not
-// instantiations of the double-precision ones (poisson.hip instantiates the solve for float):
+// instantiations of the double-precision ones (poisson.hip instantiates the solve for float, elementwise.hip the end-of-step
+// update, the infinity norm, the diagnostics' inner products and the skew-Hermitian check for float2):
 //   * k_cgemm / k_cgemm32: complex64 N x N x N product on the fp32 matrix cores (v_mfma_f32_32x32x2_f32 / 16x16x4: exact
 //     f32 fma chains at 64 flop/clk/SIMD = 157.3 TFLOP/s, MI355X_MICROARCH.md), 3M form like the fp64 kernel, with the
 //     fused epilogue of the second product (isospectral.py:499-509, 481-482, 526-534) and the fused step end;
 //     k_cgemm_ks / k_cgemm32<.., KS>: the plain product with the K range cut between groups of wavefronts of one
 //     workgroup (launches with one tile per CU);
 //   * k_cgemm_tri / k_cgemm_tri32: the second product on the upper triangle only (skew-Hermitian state), K pieces per
-//     tile exchanged through memory, the last arrival combines and runs the epilogue for the tile and its mirror image;
-//   * the end-of-step update (with the Kahan variant, isospectral.py:553-586, contraction off), the infinity
-//     norm, the diagnostics' inner products and the skew-Hermitian check on complex64 matrices.
+//     tile exchanged through memory, the last arrival combines and runs the epilogue for the tile and its mirror image.
 // The control plane is shared with the double-precision path: tagged launches, device-side exit decision on double row
 // sums (in the second product's last tile, qf_step_end.h; k_norm_decide in the two-kernel protocol), progress record --
 // see api_isomp.hip.
 #include "qf_internal.h"
 #include "qf_step_end.h"
 
-#pragma clang fp contract(off)  // Kahan summation must not be re-associated or fused; table arithmetic is the reference's
+#pragma clang fp contract(off)  // the epilogues' elementwise arithmetic is the reference's: not re-associated or fused
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
@@ -370,7 +369,7 @@ __global__ __launch_bounds__(256 * KS) void k_cgemm_ks(int N, int tiles_n, const
 // last) and runs the epilogue.  Nobody waits; the counters are monotone (`split` arrivals per executed launch).
 // 67 KiB of LDS: two workgroups share a CU, which is what lets 272 workgroups run on 256 CUs at once.
 // Below the diagonal only Whalf is written (the next first product's right operand): W and dW are read back on and
-// above the diagonal tiles only and restored once at the end of a call (k_mirror_lower_f).
+// above the diagonal tiles only and restored once at the end of a call (k_mirror_lower<float2>, elementwise.hip).
 // On 32 x 32 tiles (any N >= 64; edge tiles guarded): k_cgemm32's K loop (one 16 x 16 MFMA tile per wavefront).  Partial tiles
 // are 8 KiB, the epilogue's LDS 17 KiB: many workgroups share a CU.  (A 64 x 64-tile form of this kernel existed in
 // rounds 3-4: slower at every size -- N = 1024 71.6 against 59.2 us, N = 2048 320 against 299 -- removed in round 5.)
@@ -638,31 +637,6 @@ __global__ __launch_bounds__(256) void k_cgemm_tri32(int N, int nt, const float2
     }
 }
 
-// X[j,i] = -conj(X[i,j]) for i < j: the lower triangle of a skew-Hermitian complex64 matrix from its upper one
-__global__ __launch_bounds__(256) void k_mirror_lower_f(int N, float2 *__restrict__ X)
-{
-    constexpr int MT = 32;
-    __shared__ float2 Ts[MT][MT + 1];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int bi = blockIdx.y, bj = blockIdx.x;
-    if (bj > bi) return;
-    const int i0 = bi * MT, j0 = bj * MT;
-    for (int r = ty; r < MT; r += 8) {
-        const int gj = j0 + r, gi = i0 + tx;
-        float2 tv = make_float2(0.f, 0.f);
-        if (gj < N && gi < N) tv = X[(size_t)gj * N + gi];
-        Ts[r][tx] = tv;
-    }
-    __syncthreads();
-    for (int r = ty; r < MT; r += 8) {
-        const int gi = i0 + r, gj = j0 + tx;
-        if (gi < N && gj < N && gj < gi) {
-            const float2 t = Ts[tx][r];
-            X[(size_t)gi * N + gj] = make_float2(-t.x, t.y);
-        }
-    }
-}
-
 // The same product on 32 x 32 block tiles (N < 768): 4 wavefronts (2 x 2), one 16 x 16 tile each.
 // MFMA f32 16x16x4 lane maps: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
 // C/D[row = 4 (lane >> 4) + reg][col = lane & 15].
@@ -842,240 +816,6 @@ __global__ __launch_bounds__(256 * KS) void k_cgemm32(int N, int tiles_n, const 
     }
 }
 
-// ---- elementwise passes on complex64 matrices (the double-precision forms are in elementwise.hip)
-
-constexpr int TU = 32;
-
-__device__ void step_advance(qf_dev_state *state, qf_host_record *rec, const qf_guard &guard)
-{
-    // (as qf_step_advance of elementwise.hip: end-of-step bookkeeping by the last block of the update)
-    const bool mine = state->step_index == guard.step;
-    const bool complete = mine && (state->step_done != 0 || state->iters_this_step >= state->maxit);
-    int incomplete = 0;
-    if (complete) {
-        if (!state->step_done) state->number_of_maxit += 1;   // for-else, isospectral.py:538-540
-        rec->last_step_iters = state->iters_this_step;
-        state->step_index += 1;
-        state->iters_this_step = 0;
-        state->step_done = 0;
-        rec->resnorm = state->resnorm;
-        state->resnorm = __builtin_inf();                     // isospectral.py:470
-    } else if (mine) {
-        incomplete = 1;
-    }
-    rec->total_iterations = state->total_iterations;
-    rec->number_of_maxit = state->number_of_maxit;
-    rec->step_index = state->step_index;
-    rec->incomplete = incomplete;
-    if (state->fault == QF_FAULT_NONFINITE) rec->nonfinite = 1;      // k_norm_decide closed the call (QF_STEP_ABORTED)
-    __hip_atomic_store(&rec->seq, rec->seq + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// W += 2 (PW - PW^H) (Kahan-compensated: isospectral.py:568-586, in float32 as the reference's complex64 arrays);
-// Whalf = W + dW (the next step's first iterate), or dW = 0 with `reinitialize` (isospectral.py:471-472)
-template <bool KAHAN>
-__global__ __launch_bounds__(256) void k_update_f(int N, const float2 *__restrict__ PW, float2 *__restrict__ W, float2 *dW_a,
-                                                  float2 *dW_b, float2 *__restrict__ Whalf, float2 *__restrict__ kc,
-                                                  int reinitialize, qf_guard guard, qf_dev_state *state, qf_host_record *rec,
-                                                  unsigned *ticket)
-{
-    const bool due = qf_guard_step_end(guard);
-    if (due) {
-        float2 *dWc = (guard.state && guard.state->dw_parity) ? dW_b : dW_a;
-        const float2 *dW = reinitialize ? nullptr : dWc;
-        __shared__ float2 Ts[TU][TU + 1];
-        const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-        const int i0 = blockIdx.y * TU, j0 = blockIdx.x * TU;
-        for (int r = ty; r < TU; r += 8) {
-            const int gj = j0 + r, gi = i0 + tx;
-            float2 tv = make_float2(0.f, 0.f);
-            if (gj < N && gi < N) tv = PW[(size_t)gj * N + gi];
-            Ts[r][tx] = tv;
-        }
-        __syncthreads();
-        for (int r = ty; r < TU; r += 8) {
-            const int gi = i0 + r, gj = j0 + tx;
-            if (gi < N && gj < N) {
-                const size_t e = (size_t)gi * N + gj;
-                const float2 pw = PW[e];
-                const float2 pwt = Ts[tx][r];
-                const float dr = 2.0f * (pw.x - pwt.x);       // conj_subtract_ then `PWcomm *= 2` (:503,547)
-                const float di = 2.0f * (pw.y + pwt.y);
-                float2 w = W[e];
-                if (KAHAN) {
-                    float2 c = kc[e];
-                    const float yr = dr - c.x, yi = di - c.y;
-                    const float tr = w.x + yr, ti = w.y + yi;
-                    c.x = (tr - w.x) - yr;
-                    c.y = (ti - w.y) - yi;
-                    kc[e] = c;
-                    w.x = tr;
-                    w.y = ti;
-                } else {
-                    w.x += dr;
-                    w.y += di;
-                }
-                W[e] = w;
-                if (dW) {
-                    const float2 d = dW[e];
-                    Whalf[e] = make_float2(w.x + d.x, w.y + d.y);
-                } else {
-                    Whalf[e] = w;
-                    dWc[e] = make_float2(0.f, 0.f);
-                }
-            }
-        }
-    }
-    if (state) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            if (atomicAdd(&ticket[1 + blockIdx.y], 1u) == gridDim.x - 1) {
-                ticket[1 + blockIdx.y] = 0;
-                if (atomicAdd(&ticket[0], 1u) == gridDim.y - 1) {
-                    ticket[0] = 0;
-                    step_advance(state, rec, guard);
-                }
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// rowsum[i] = sum_j |A[i,j]| (moduli in float32 as np.abs of a complex64 array, sums in double)
-__global__ __launch_bounds__(256) void k_row_abs_sum_f(int N, const float2 *__restrict__ A, double *__restrict__ rowsum)
-{
-    __shared__ double part[4];
-    const int i = blockIdx.x;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < N; j += 256) {
-        const float2 z = A[(size_t)i * N + j];
-        s += (double)hypotf(z.x, z.y);
-    }
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) rowsum[i] = (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// out[0] = max_i rowsum[i] (NaN-propagating), one block
-__global__ __launch_bounds__(1024) void k_max_rows_f(int N, const double *__restrict__ rowsum, double *__restrict__ out)
-{
-    __shared__ double part[16];
-    __shared__ int nanp[16];
-    double m = 0.0;
-    int nan = 0;
-    for (int i = threadIdx.x; i < N; i += 1024) {
-        const double s = rowsum[i];
-        if (s != s) nan = 1; else m = fmax(m, s);
-    }
-    m = wave_max_d(m);
-    const double nn = wave_max_d((double)nan);
-    if ((threadIdx.x & 63) == 0) {
-        part[threadIdx.x >> 6] = m;
-        nanp[threadIdx.x >> 6] = nn > 0.0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = 0.0;
-        bool anynan = false;
-        for (int w = 0; w < 16; ++w) {
-            if (nanp[w]) anynan = true;
-            r = fmax(r, part[w]);
-        }
-        out[0] = anynan ? __builtin_nan("") : r;
-    }
-}
-
-// partial[b] = sum Re(A conj(B)), partial[1024 + b] = sum |A|^2 over the entries of block b (products in
-// float32, sums in double); k_sum2_f adds the partials in block order
-__global__ __launch_bounds__(256) void k_inner2_partial_f(size_t n, const float2 *__restrict__ A, const float2 *__restrict__ B,
-                                                          double *__restrict__ partial)
-{
-    __shared__ double p0[4], p1[4];
-    double s0 = 0.0, s1 = 0.0;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const float2 a = A[e], b = B[e];
-        s0 += (double)(a.x * b.x + a.y * b.y);
-        s1 += (double)(a.x * a.x + a.y * a.y);
-    }
-    s0 = wave_sum_d(s0);
-    s1 = wave_sum_d(s1);
-    if ((threadIdx.x & 63) == 0) {
-        p0[threadIdx.x >> 6] = s0;
-        p1[threadIdx.x >> 6] = s1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = (p0[0] + p0[1]) + (p0[2] + p0[3]);
-        partial[1024 + blockIdx.x] = (p1[0] + p1[1]) + (p1[2] + p1[3]);
-    }
-}
-
-__global__ __launch_bounds__(64) void k_sum2_f(int n, const double *__restrict__ partial, double *__restrict__ out)
-{
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) {
-        s0 += partial[i];
-        s1 += partial[1024 + i];
-    }
-    s0 = wave_sum_d(s0);
-    s1 = wave_sum_d(s1);
-    if (threadIdx.x == 0) {
-        out[0] = s0;
-        out[1] = s1;
-    }
-}
-
-// defect[b] = max |A[i,j] + conj(A[j,i])| over the rows of block b (NaN -> inf)
-__global__ __launch_bounds__(256) void k_skew_defect_f(int N, const float2 *__restrict__ A, double *__restrict__ defect)
-{
-    __shared__ double sd[4];
-    double d = 0.0;
-    bool nan = false;
-    for (int i = blockIdx.x; i < N; i += gridDim.x)
-        for (int j = threadIdx.x; j < N; j += 256) {
-            const float2 x = A[(size_t)i * N + j], y = A[(size_t)j * N + i];
-            const float dr = x.x + y.x, di = x.y - y.y;
-            const double dd = fmax(fabs((double)dr), fabs((double)di));
-            if (dd != dd) nan = true;
-            d = fmax(d, dd);
-        }
-    if (nan) d = __builtin_inf();
-    d = wave_max_d(d);
-    if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = d;
-    __syncthreads();
-    if (threadIdx.x == 0) defect[blockIdx.x] = fmax(fmax(sd[0], sd[1]), fmax(sd[2], sd[3]));
-}
-
-__global__ void k_max_partials_f(int n, const double *__restrict__ p, double *__restrict__ out)
-{
-    double d = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) d = fmax(d, p[i]);
-    d = wave_max_d(d);
-    if (threadIdx.x == 0) out[0] = d;
-}
-
-// out = a X + b Y (elementwise, float32)
-__global__ __launch_bounds__(256) void k_lincomb_f(size_t n, float a, const float2 *X, float b, const float2 *Y, float2 *out)
-{
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const float2 x = X[e], y = Y[e];
-        out[e] = make_float2(a * x.x + b * y.x, a * x.y + b * y.y);
-    }
-}
-
 }  // namespace
 
 // Tile sizes of the complex64 products.  The 32 x 32 kernels are small (18-34 KiB of LDS, 50-82 registers): several
@@ -1136,8 +876,8 @@ int qf_c64_alloc(qf_ctx *ctx)
     }
     ctx->c64 = f;
     // float32 coefficient table (bc = True) and its factorisation, once per N (cpu.py:725)
-    QF_TRY(qf_launch_lap_table_f32(ctx, 1, f->lap));
-    QF_TRY(qf_launch_build_factors_f32(ctx, f->lap, f->tab));
+    QF_TRY(qf_launch_lap_table(ctx, 1, f->lap));
+    QF_TRY(qf_launch_build_factors(ctx, f->lap, f->tab));
     return QF_OK;
 }
 
@@ -1302,73 +1042,6 @@ int qf_launch_cgemm_tri(qf_ctx *ctx, const float2 *A, const float2 *B, const qf_
              ep.fused ? "fused (last tile decides)" : "two-kernel");
     if (N % SBM == 0) hipLaunchKernelGGL(k_cgemm_tri32<true>, dim3(grid), dim3(256), ST_SMEM, ctx->stream, N, nt, A, B, ep, guard, sx);
     else hipLaunchKernelGGL(k_cgemm_tri32<false>, dim3(grid), dim3(256), ST_SMEM, ctx->stream, N, nt, A, B, ep, guard, sx);
-    QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int qf_launch_mirror_lower_f32(qf_ctx *ctx, float2 *X)
-{
-    const int tiles = (ctx->N + 31) / 32;
-    hipLaunchKernelGGL(k_mirror_lower_f, dim3(tiles, tiles), dim3(256), 0, ctx->stream, ctx->N, X);
-    QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int qf_launch_update_f32(qf_ctx *ctx, const float2 *PW, float2 *W, float2 *dW_a, float2 *dW_b, float2 *Whalf, float2 *kahan_c,
-                         int reinitialize, qf_guard guard)
-{
-    const int N = ctx->N;
-    dim3 grid((N + TU - 1) / TU, (N + TU - 1) / TU), block(256);
-    if (kahan_c)
-        hipLaunchKernelGGL(k_update_f<true>, grid, block, 0, ctx->stream, N, PW, W, dW_a, dW_b, Whalf, kahan_c, reinitialize, guard,
-                           guard.state ? ctx->state : nullptr, ctx->host_rec, ctx->ticket);
-    else
-        hipLaunchKernelGGL(k_update_f<false>, grid, block, 0, ctx->stream, N, PW, W, dW_a, dW_b, Whalf, kahan_c, reinitialize, guard,
-                           guard.state ? ctx->state : nullptr, ctx->host_rec, ctx->ticket);
-    QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int qf_launch_norm_inf_f32(qf_ctx *ctx, const float2 *A, double *out_dev)
-{
-    hipLaunchKernelGGL(k_row_abs_sum_f, dim3(ctx->N), dim3(256), 0, ctx->stream, ctx->N, A, ctx->rowsum);
-    QF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_max_rows_f, dim3(1), dim3(1024), 0, ctx->stream, ctx->N, ctx->rowsum, out_dev);
-    QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int qf_launch_inner2_f32(qf_ctx *ctx, const float2 *A, const float2 *B, double *out_dev)
-{
-    const size_t n = (size_t)ctx->N * ctx->N;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 1024) blocks = 1024;
-    double *partial = ctx->scalars + 64;    // [2][1024]
-    hipLaunchKernelGGL(k_inner2_partial_f, dim3(blocks), dim3(256), 0, ctx->stream, n, A, B, partial);
-    QF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_sum2_f, dim3(1), dim3(64), 0, ctx->stream, blocks, partial, out_dev);
-    QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int qf_launch_skew_defect_f32(qf_ctx *ctx, const float2 *A, double *out_dev)
-{
-    const int N = ctx->N;
-    const int blocks = N < 1024 ? N : 1024;
-    double *partial = ctx->scalars + 64;
-    hipLaunchKernelGGL(k_skew_defect_f, dim3(blocks), dim3(256), 0, ctx->stream, N, A, partial);
-    QF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_max_partials_f, dim3(1), dim3(64), 0, ctx->stream, blocks, partial, out_dev);
-    QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int qf_launch_lincomb_f32(qf_ctx *ctx, float a, const float2 *X, float b, const float2 *Y, float2 *out)
-{
-    const size_t n = (size_t)ctx->N * ctx->N;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_lincomb_f, dim3(blocks), dim3(256), 0, ctx->stream, n, a, X, b, Y, out);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }
