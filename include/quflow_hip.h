@@ -241,7 +241,7 @@ int qf_erk_states_hooked(qf_ctx *ctx, void *states_host, int k, int method, doub
 /* ---- spherical-harmonics <-> matrix transforms (quflow/quantization.py).  The quantization
  *      basis (compute_basis, quantization.py:68-113: N(N+1)(2N+1)/6 doubles, block m row-major at
  *      basis_break_index(m, N)) is uploaded once and stays resident in HBM; a transform is one
- *      HBM-bound sweep over it.  A NULL matrix pointer means "the ctx state W" (initial data /
+ *      HBM-bound sweep over it (or, after qf_basis_stream, rebuilds the blocks it needs slab by slab).  A NULL matrix pointer means "the ctx state W" (initial data /
  *      'shr' output of a resident trajectory without moving W over PCIe). ------------------ */
 int qf_basis_upload(qf_ctx *ctx, const double *basis_host, long long count);
 /* compute_basis(N) (quantization.py:68-113) on the device, straight into the resident copy: the
@@ -250,6 +250,20 @@ int qf_basis_upload(qf_ctx *ctx, const double *basis_host, long long count);
  * LAPACK's tridiagonal eigensolver), scaled and oriented as quantization.py:45-65,99-106. */
 int qf_basis_compute(qf_ctx *ctx);
 int qf_basis_download(qf_ctx *ctx, double *basis_host, long long count);
+/* The streamed form, a per-context mode.  slab_bytes > 0: from now on qf_shr2mat, qf_mat2shr, qf_shc2mat and qf_mat2shc
+ * (their NULL forms included) do not read a resident basis.  Each call rebuilds the blocks it needs -- of every block
+ * m < Nmax only the columns j < Nmax - m, by the same per-column arithmetic as qf_basis_compute, so the same bits -- into a
+ * slab of at most slab_bytes on the device and applies them there, whole blocks in m order, slab after slab: memory
+ * stays near N^2 instead of N^3/3, and the results equal the resident path's bit for bit.  They stream whether or not
+ * the context also holds a resident basis.  A call whose block m = 0 (N x Nmax doubles) does not fit slab_bytes fails
+ * with QF_ERR_INVALID before it touches anything.  The slab is grown on demand and freed with the context.
+ * slab_bytes == 0: back to the resident basis (the default; the transforms then need qf_basis_upload or
+ * qf_basis_compute).  Negative: QF_ERR_INVALID.  qf_basis_download always needs the resident basis. */
+int qf_basis_stream(qf_ctx *ctx, long long slab_bytes);
+/* The streamed form's plan, host only: how many slabs a transform with band limit Nmax (1..N) takes under slab_bytes,
+ * and the first block of each of them in first_block[0 .. min(count, capacity) - 1] (first_block may be NULL).  Slabs
+ * hold whole blocks in m order, as many as fit.  Returns the count, or -QF_ERR_INVALID when block 0 does not fit. */
+int qf_basis_slab_plan(int N, int Nmax, long long slab_bytes, int *first_block, int capacity);
 /* shr2mat_(omega, basis, W_out), quantization.py:188-245 (W_out zeroed first as in shr2mat, :474);
  * n_omega < N^2 band-limits to el < int(sqrt(n_omega)) (:204-208) */
 int qf_shr2mat(qf_ctx *ctx, const double *omega_host, long long n_omega, void *W_host);

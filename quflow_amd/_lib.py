@@ -116,6 +116,9 @@ SIGNATURES = {
     "qf_basis_upload": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong]),
     "qf_basis_compute": (ctypes.c_int, [_vp]),
     "qf_basis_download": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong]),
+    "qf_basis_stream": (ctypes.c_int, [_vp, ctypes.c_longlong]),
+    "qf_basis_slab_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.c_int]),
     "qf_shr2mat": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, _vp]),
     "qf_mat2shr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_longlong]),
     "qf_shc2mat": (ctypes.c_int, [_vp, _vp, _vp]),

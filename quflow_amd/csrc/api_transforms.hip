@@ -24,6 +24,16 @@ static int need_basis(qf_ctx *ctx, const char *who)
     return QF_OK;
 }
 
+static int alloc_stage(qf_ctx *ctx);
+
+// what a transform reads its blocks from: the streamed form (qf_basis_stream > 0) needs only the staging buffers, the
+// resident one the basis
+static int need_source(qf_ctx *ctx, const char *who)
+{
+    if (ctx->slab_budget > 0) return alloc_stage(ctx);
+    return need_basis(ctx, who);
+}
+
 // band limit of a coefficient array with n entries: quantization.py:204-208,294-298 (parallel form)
 static int band_limit(int N, long long n)
 {
@@ -48,14 +58,43 @@ int qf_basis_upload(qf_ctx *ctx, const double *basis_host, long long count)
     return QF_OK;
 }
 
+// the m-major staging vectors and the device coefficients: every transform needs them, resident or streamed
+static int alloc_stage(qf_ctx *ctx)
+{
+    const long long N = ctx->N;
+    if (!ctx->sh_stage) QF_HIP(hipMalloc((void **)&ctx->sh_stage, (size_t)4 * (N * (N + 1) / 2) * sizeof(cplx)));
+    if (!ctx->sh_omega) QF_HIP(hipMalloc((void **)&ctx->sh_omega, (size_t)2 * N * N * sizeof(double)));
+    return QF_OK;
+}
+
 static int alloc_sh(qf_ctx *ctx)
 {
     const long long N = ctx->N;
     const long long want = N * (N + 1) * (2 * N + 1) / 6;
     if (!ctx->basis) QF_HIP(hipMalloc((void **)&ctx->basis, (size_t)want * sizeof(double)));
-    if (!ctx->sh_stage) QF_HIP(hipMalloc((void **)&ctx->sh_stage, (size_t)4 * (N * (N + 1) / 2) * sizeof(cplx)));
-    if (!ctx->sh_omega) QF_HIP(hipMalloc((void **)&ctx->sh_omega, (size_t)2 * N * N * sizeof(double)));
+    return alloc_stage(ctx);
+}
+
+int qf_basis_stream(qf_ctx *ctx, long long slab_bytes)
+{
+    QF_TRY(check_ctx(ctx));
+    if (slab_bytes < 0) {
+        qf_set_error("qf_basis_stream: negative slab budget %lld", slab_bytes);
+        return QF_ERR_INVALID;
+    }
+    ctx->slab_budget = slab_bytes;
     return QF_OK;
+}
+
+int qf_basis_slab_plan(int N, int Nmax, long long slab_bytes, int *first_block, int capacity)
+{
+    std::vector<int> first;
+    long long max_bytes = 0;
+    const int rc = qf_slab_plan(N, Nmax, slab_bytes, first, &max_bytes);
+    if (rc != QF_OK) return -rc;
+    const int nslabs = (int)first.size() - 1;
+    for (int s = 0; first_block && s < nslabs && s < capacity; ++s) first_block[s] = first[s];
+    return nslabs;
 }
 
 int qf_basis_compute(qf_ctx *ctx)
@@ -93,7 +132,7 @@ int qf_basis_download(qf_ctx *ctx, double *basis_host, long long count)
 int qf_shr2mat(qf_ctx *ctx, const double *omega_host, long long n_omega, void *W_host)
 {
     QF_TRY(check_ctx(ctx));
-    QF_TRY(need_basis(ctx, "qf_shr2mat"));
+    QF_TRY(need_source(ctx, "qf_shr2mat"));
     if (n_omega < 1) {
         qf_set_error("qf_shr2mat: empty coefficient array");
         return QF_ERR_INVALID;
@@ -117,7 +156,7 @@ int qf_shr2mat(qf_ctx *ctx, const double *omega_host, long long n_omega, void *W
 int qf_mat2shr(qf_ctx *ctx, const void *W_host, double *omega_host, long long n_omega)
 {
     QF_TRY(check_ctx(ctx));
-    QF_TRY(need_basis(ctx, "qf_mat2shr"));
+    QF_TRY(need_source(ctx, "qf_mat2shr"));
     if (n_omega < 1) {
         qf_set_error("qf_mat2shr: empty coefficient array");
         return QF_ERR_INVALID;
@@ -145,7 +184,7 @@ int qf_mat2shr(qf_ctx *ctx, const void *W_host, double *omega_host, long long n_
 int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host)
 {
     QF_TRY(check_ctx(ctx));
-    QF_TRY(need_basis(ctx, "qf_shc2mat"));
+    QF_TRY(need_source(ctx, "qf_shc2mat"));
     if (!omega_host) {
         qf_set_error("qf_shc2mat: null coefficient array");
         return QF_ERR_INVALID;
@@ -164,7 +203,7 @@ int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host)
 int qf_mat2shc(qf_ctx *ctx, const void *W_host, void *omega_host)
 {
     QF_TRY(check_ctx(ctx));
-    QF_TRY(need_basis(ctx, "qf_mat2shc"));
+    QF_TRY(need_source(ctx, "qf_mat2shc"));
     if (!omega_host) {
         qf_set_error("qf_mat2shc: null coefficient array");
         return QF_ERR_INVALID;

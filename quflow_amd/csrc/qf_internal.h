@@ -344,6 +344,10 @@ struct qf_ctx {
     cplx *sh_stage = nullptr;    // 4 x N(N+1)/2 complex: packed coefficient / diagonal vectors
     double *sh_omega = nullptr;  // 2 N^2 doubles: omega on the device (real or complex)
     long long sh_shr_count = 0;  // real coefficients sh_omega holds (the last qf_mat2shr / qf_shr2mat); 0: none
+    long long slab_budget = 0;   // qf_basis_stream: > 0 the transforms rebuild the basis blocks they need into slabs of at
+                                 // most this many bytes instead of reading ctx->basis; 0 resident (the default)
+    double *slab = nullptr;      // the streamed form's slab: grown on demand to the largest slab planned, never shrunk
+    size_t slab_cap = 0;         // bytes ctx->slab has
     qf_sht sht;                  // spherical-harmonic synthesis scratch (sht.hip), grown with the bandwidth
 
     double *rowpart = nullptr;   // [tiles_n][N] partial row sums from the GEMM2 epilogue
@@ -515,6 +519,18 @@ int qf_launch_zgemm(qf_ctx *ctx, const cplx *A, const cplx *B, cplx *C, const qf
 
 // ---- quantization.hip (device pointers; Nmax = band limit el < Nmax)
 int qf_launch_basis(qf_ctx *ctx, double *basis_dev);   // compute_basis on the device
+// The streamed form keeps, of every block m < Nmax, the columns j < J_m = Nmax - m, row-major (N - m) x J_m, blocks in m
+// order: block m starts at qf_slab_prefix(N, Nmax, m) - qf_slab_prefix(N, Nmax, m0) doubles into a slab that begins with
+// block m0.  qf_slab_prefix(m) = sum_{i<m} (N - i)(Nmax - i), in closed form (exact in 64-bit integers for N <= 8192).
+__host__ __device__ inline long long qf_slab_prefix(int N, int Nmax, int m)
+{
+    const long long a = m, n = N, k = Nmax;
+    return a * n * k - (n + k) * (a * (a - 1) / 2) + (a - 1) * a * (2 * a - 1) / 6;
+}
+// Slabs of a streamed transform with band limit Nmax under a budget of slab_bytes: whole blocks, in m order, as many as fit.
+// first[s] is the first block of slab s, first.back() == Nmax closes the last one; *max_bytes = the largest slab.
+// QF_ERR_INVALID (error set) when block 0, N x Nmax doubles, is larger than the budget.
+int qf_slab_plan(int N, int Nmax, long long slab_bytes, std::vector<int> &first, long long *max_bytes);
 int qf_launch_shr2mat(qf_ctx *ctx, int Nmax, const double *omega_dev, cplx *W_dev);
 int qf_launch_mat2shr(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev);
 int qf_launch_shc2mat(qf_ctx *ctx, const double *omega_dev, cplx *W_dev);

@@ -4,7 +4,10 @@
 //      shr2mat_/shc2mat_ :  diag_m = B_m @ x_m          (quantization.py:188-245, 331-365)
 //      mat2shr_/mat2shc_ :  z_m    = diag_m @ B_m       (quantization.py:286-327, 368-396)
 // i.e. one sweep over the N^3/3-entry basis (2.9 GB at N=1024) per transform: HBM-bound.
-// The basis lives in HBM for the life of the context (qf_basis_upload).
+// The basis lives in HBM for the life of the context (qf_basis_upload), or -- the streamed form, qf_basis_stream, for
+// the N where it cannot (183 GB at N=4096) -- it is not stored at all: every call rebuilds the blocks m < Nmax, columns
+// j < Nmax - m, into a bounded slab (k_basis_slab, the same column arithmetic as k_basis) and applies them there with
+// the slab instantiations of the two main kernels, slab after slab (whole blocks in m order, qf_slab_plan).
 //
 // Layouts.  omega is indexed el^2 + el + m (quflow/utils.py:91-105): for fixed m its entries
 // are strided by ~2 el, one cache line each.  Small pack/unpack kernels therefore move the
@@ -62,14 +65,13 @@ __device__ __forceinline__ double direct_lap_off(int N, int m, int k)   // coupl
     return fabs(c) > 1e-10 ? -c : 0.0;
 }
 
-__global__ __launch_bounds__(256) void k_basis(int N, double *__restrict__ basis)
+// Column j of block m (n = N - m entries, entry k at B[k * ld]): the twisted factorisation, its Rayleigh-corrected
+// repeat, the scaling and the orientation.  Both basis kernels call this one function, so a column built into a slab
+// (ld = J_m) has the same bits as the resident one (ld = n): the arithmetic never sees ld.
+__device__ __forceinline__ void basis_column(int N, int m, int j, double *__restrict__ B, size_t ld)
 {
-    const int m = blockIdx.y;
     const int n = N - m;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    double *B = basis + basis_offset(m, N) + j;     // entry k of this vector: B[k*n]
-    const size_t nn = (size_t)n;
+    const size_t nn = ld;
     const long long el = m + j;
     double lambda = -(double)(el * (el + 1));
     // a pivot this small is replaced (LAPACK's pivmin idea): |T| ~ N^2/2, so 1e-30 |T| is far below
@@ -155,6 +157,26 @@ __global__ __launch_bounds__(256) void k_basis(int N, double *__restrict__ basis
     for (int k = 0; k < n; ++k) B[k * nn] *= scale;
 }
 
+__global__ __launch_bounds__(256) void k_basis(int N, double *__restrict__ basis)
+{
+    const int m = blockIdx.y;
+    const int n = N - m;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    basis_column(N, m, j, basis + basis_offset(m, N) + j, (size_t)n);
+}
+
+// ---- the streamed form: blocks m0 <= m < m0 + gridDim.y of a band limit Nmax, only the columns j < J_m = Nmax - m
+// that carry coefficients, block m row-major (N - m) x J_m at slab_prefix(m) - slab_prefix(m0) of a bounded slab
+__global__ __launch_bounds__(256) void k_basis_slab(int N, int Nmax, int m0, double *__restrict__ slab)
+{
+    const int m = m0 + blockIdx.y;
+    const int J = Nmax - m;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= J) return;
+    basis_column(N, m, j, slab + (qf_slab_prefix(N, Nmax, m) - qf_slab_prefix(N, Nmax, m0)) + j, (size_t)J);
+}
+
 constexpr int MODE_SHR = 0, MODE_SHC = 1;
 
 // ---- coefficients -> m-major vectors x (shr: one complex vector per m; shc: two)
@@ -183,22 +205,37 @@ __global__ void k_pack_coeffs(int N, int Nmax, const double *__restrict__ omega,
     }
 }
 
-// ---- y_m = B_m[:, :J] @ x_m and the assignment to the diagonals of W (followed by W *= 1j)
-template <int MODE>
-__global__ __launch_bounds__(256) void k_block_matvec(int N, int Nmax, const double *__restrict__ basis,
+// Where block m of a launch starts and its row stride: the resident basis (SLAB false: basis_offset, ld = N - m) or a
+// slab of the streamed form (blocks from m0 on, ld = J_m).  The summation orders below depend on row and column indices
+// only, so both sources give the same bits.
+template <bool SLAB>
+__device__ __forceinline__ const double *block_base(const double *basis, int N, int Nmax, int m0, int m, size_t &ld)
+{
+    if (SLAB) {
+        ld = (size_t)(Nmax - m);
+        return basis + (qf_slab_prefix(N, Nmax, m) - qf_slab_prefix(N, Nmax, m0));
+    }
+    ld = (size_t)(N - m);
+    return basis + basis_offset(m, N);
+}
+
+// ---- y_m = B_m[:, :J] @ x_m and the assignment to the diagonals of W (followed by W *= 1j); blocks m0 + blockIdx.y
+template <int MODE, bool SLAB>
+__global__ __launch_bounds__(256) void k_block_matvec(int N, int Nmax, int m0, const double *__restrict__ basis,
                                                        const cplx *__restrict__ x0, const cplx *__restrict__ x1,
                                                        cplx *__restrict__ W)
 {
     constexpr int RW = 8;                      // rows per wave: 8 x 4 independent 512-byte row loads in flight
     constexpr int ROWS = 4 * RW, CH = 256, NV = (MODE == MODE_SHC) ? 2 : 1;
     __shared__ cplx xs[NV][CH];
-    const int m = blockIdx.y;
+    const int m = m0 + blockIdx.y;
     const int n = N - m;
     const int row0 = blockIdx.x * ROWS;
     if (m >= Nmax || row0 >= n) return;
     const int J = Nmax - m;                   // columns that carry coefficients
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double *B = basis + basis_offset(m, N);
+    size_t ld;
+    const double *B = block_base<SLAB>(basis, N, Nmax, m0, m, ld);
     const size_t xo = mmajor_offset(m, N);
     double acc[RW][NV][2];
 #pragma unroll
@@ -211,7 +248,7 @@ __global__ __launch_bounds__(256) void k_block_matvec(int N, int Nmax, const dou
     for (int r = 0; r < RW; ++r) {
         int i = row0 + wave * RW + r;
         if (i > n - 1) i = n - 1;
-        Brow[r] = B + (size_t)i * n;
+        Brow[r] = B + (size_t)i * ld;
     }
     for (int c0 = 0; c0 < J; c0 += CH) {
         __syncthreads();
@@ -290,16 +327,16 @@ __global__ void k_pack_diags(int N, int Nmax, const cplx *__restrict__ W, cplx *
     if (MODE == MODE_SHC && m != 0) d1[o] = W[(size_t)k * N + (k + m)];
 }
 
-// ---- z_m[j] = sum_k d_m[k] B_m[k, j], j < J
-template <int MODE>
-__global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, const double *__restrict__ basis,
+// ---- z_m[j] = sum_k d_m[k] B_m[k, j], j < J; blocks m0 + blockIdx.y
+template <int MODE, bool SLAB>
+__global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, int m0, const double *__restrict__ basis,
                                                        const cplx *__restrict__ d0, const cplx *__restrict__ d1,
                                                        cplx *__restrict__ z0, cplx *__restrict__ z1)
 {
     constexpr int NV = (MODE == MODE_SHC) ? 2 : 1, KCH = 256;
     __shared__ cplx ds[NV][KCH];
     __shared__ double part[4][NV][2][64];
-    const int m = blockIdx.y;
+    const int m = m0 + blockIdx.y;
     const int n = N - m;
     const int J = Nmax - m;
     const int j0 = blockIdx.x * 64;
@@ -307,7 +344,8 @@ __global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, const dou
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = j0 + lane;
     const bool live = j < J;
-    const double *B = basis + basis_offset(m, N) + (live ? j : j0);
+    size_t ld;
+    const double *B = block_base<SLAB>(basis, N, Nmax, m0, m, ld) + (live ? j : j0);
     const size_t dof = mmajor_offset(m, N);
     double acc[NV][2];
 #pragma unroll
@@ -332,7 +370,7 @@ __global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, const dou
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = kk + 4 * u;
-                b[u] = (k < kend) ? B[(size_t)(k0 + k) * n] : 0.0;
+                b[u] = (k < kend) ? B[(size_t)(k0 + k) * ld] : 0.0;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -399,18 +437,56 @@ __global__ void k_unpack_coeffs(int N, int Nmax, const cplx *__restrict__ z0, co
     }
 }
 
+// The streamed form's slabs for band limit Nmax, planned and the slab grown to the largest of them (hipFree waits for the
+// device).  Called before anything is launched, so a refusal leaves W and the coefficients as they were.
+int reserve_slabs(qf_ctx *ctx, int Nmax, std::vector<int> &first)
+{
+    long long need = 0;
+    QF_TRY(qf_slab_plan(ctx->N, Nmax, ctx->slab_budget, first, &need));
+    if ((size_t)need > ctx->slab_cap) {
+        if (ctx->slab) (void)hipFree(ctx->slab);
+        ctx->slab = nullptr;
+        ctx->slab_cap = 0;
+        QF_HIP(hipMalloc((void **)&ctx->slab, (size_t)need));
+        ctx->slab_cap = (size_t)need;
+    }
+    return QF_OK;
+}
+
+// blocks first[s] <= m < first[s + 1] of the band limit Nmax into ctx->slab
+int generate_slab(qf_ctx *ctx, int Nmax, int m0, int m1)
+{
+    dim3 grid((Nmax - m0 + 255) / 256, m1 - m0);
+    hipLaunchKernelGGL(k_basis_slab, grid, dim3(256), 0, ctx->stream, ctx->N, Nmax, m0, ctx->slab);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+// Pack once; then either one launch over the resident basis, or generate -> apply for each slab (ctx->slab_budget > 0)
 template <int MODE>
 int forward(qf_ctx *ctx, int Nmax, const double *omega_dev, cplx *W_dev)
 {
     const int N = ctx->N;
     cplx *x0 = ctx->sh_stage, *x1 = ctx->sh_stage + (size_t)N * (N + 1) / 2;
+    std::vector<int> first;
+    if (ctx->slab_budget > 0) QF_TRY(reserve_slabs(ctx, Nmax, first));
     QF_HIP(hipMemsetAsync(W_dev, 0, (size_t)N * N * sizeof(cplx), ctx->stream));   // np.zeros((N,N)), quantization.py:474
     dim3 gp((Nmax + 255) / 256, Nmax);
     hipLaunchKernelGGL(k_pack_coeffs<MODE>, gp, dim3(256), 0, ctx->stream, N, Nmax, omega_dev, x0, x1);
     QF_HIP(hipGetLastError());
-    dim3 gm((N + 31) / 32, Nmax);   // 32 rows per workgroup
-    hipLaunchKernelGGL(k_block_matvec<MODE>, gm, dim3(256), 0, ctx->stream, N, Nmax, ctx->basis, x0, x1, W_dev);
-    QF_HIP(hipGetLastError());
+    if (ctx->slab_budget == 0) {
+        dim3 gm((N + 31) / 32, Nmax);   // 32 rows per workgroup
+        hipLaunchKernelGGL((k_block_matvec<MODE, false>), gm, dim3(256), 0, ctx->stream, N, Nmax, 0, ctx->basis, x0, x1, W_dev);
+        QF_HIP(hipGetLastError());
+        return QF_OK;
+    }
+    for (size_t s = 0; s + 1 < first.size(); ++s) {
+        const int m0 = first[s], m1 = first[s + 1];
+        QF_TRY(generate_slab(ctx, Nmax, m0, m1));
+        dim3 gm((N + 31) / 32, m1 - m0);
+        hipLaunchKernelGGL((k_block_matvec<MODE, true>), gm, dim3(256), 0, ctx->stream, N, Nmax, m0, ctx->slab, x0, x1, W_dev);
+        QF_HIP(hipGetLastError());
+    }
     return QF_OK;
 }
 
@@ -420,12 +496,24 @@ int backward(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev)
     const int N = ctx->N;
     const size_t half = (size_t)N * (N + 1) / 2;
     cplx *d0 = ctx->sh_stage, *d1 = d0 + half, *z0 = d1 + half, *z1 = z0 + half;
+    std::vector<int> first;
+    if (ctx->slab_budget > 0) QF_TRY(reserve_slabs(ctx, Nmax, first));
     dim3 gp((N + 255) / 256, Nmax);
     hipLaunchKernelGGL(k_pack_diags<MODE>, gp, dim3(256), 0, ctx->stream, N, Nmax, W_dev, d0, d1);
     QF_HIP(hipGetLastError());
-    dim3 gm((Nmax + 63) / 64, Nmax);
-    hipLaunchKernelGGL(k_block_vecmat<MODE>, gm, dim3(256), 0, ctx->stream, N, Nmax, ctx->basis, d0, d1, z0, z1);
-    QF_HIP(hipGetLastError());
+    if (ctx->slab_budget == 0) {
+        dim3 gm((Nmax + 63) / 64, Nmax);
+        hipLaunchKernelGGL((k_block_vecmat<MODE, false>), gm, dim3(256), 0, ctx->stream, N, Nmax, 0, ctx->basis, d0, d1, z0, z1);
+        QF_HIP(hipGetLastError());
+    } else {
+        for (size_t s = 0; s + 1 < first.size(); ++s) {
+            const int m0 = first[s], m1 = first[s + 1];
+            QF_TRY(generate_slab(ctx, Nmax, m0, m1));
+            dim3 gm((Nmax - m0 + 63) / 64, m1 - m0);
+            hipLaunchKernelGGL((k_block_vecmat<MODE, true>), gm, dim3(256), 0, ctx->stream, N, Nmax, m0, ctx->slab, d0, d1, z0, z1);
+            QF_HIP(hipGetLastError());
+        }
+    }
     dim3 gu((Nmax + 255) / 256, Nmax);
     hipLaunchKernelGGL(k_unpack_coeffs<MODE>, gu, dim3(256), 0, ctx->stream, N, Nmax, z0, z1, omega_dev);
     QF_HIP(hipGetLastError());
@@ -433,6 +521,35 @@ int backward(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev)
 }
 
 }  // namespace
+
+int qf_slab_plan(int N, int Nmax, long long slab_bytes, std::vector<int> &first, long long *max_bytes)
+{
+    first.clear();
+    *max_bytes = 0;
+    if (N < 1 || Nmax < 1 || Nmax > N) {
+        qf_set_error("qf_slab_plan: band limit Nmax=%d outside 1..N=%d", Nmax, N);
+        return QF_ERR_INVALID;
+    }
+    const long long block0 = 8LL * N * Nmax;     // the largest block: every other one is smaller
+    if (slab_bytes < block0) {
+        qf_set_error("streamed basis: block m=0 for N=%d, Nmax=%d takes %lld bytes, more than the slab budget of %lld bytes",
+                     N, Nmax, block0, slab_bytes);
+        return QF_ERR_INVALID;
+    }
+    int m0 = 0;
+    first.push_back(0);
+    for (int m = 1; m <= Nmax; ++m) {
+        const long long bytes = 8 * (qf_slab_prefix(N, Nmax, m) - qf_slab_prefix(N, Nmax, m0));
+        const bool last = (m == Nmax);
+        const long long next = last ? 0 : 8LL * (N - m) * (Nmax - m);
+        if (last || bytes + next > slab_bytes) {
+            if (bytes > *max_bytes) *max_bytes = bytes;
+            first.push_back(m);
+            m0 = m;
+        }
+    }
+    return QF_OK;
+}
 
 int qf_launch_basis(qf_ctx *ctx, double *basis_dev)
 {

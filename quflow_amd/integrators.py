@@ -929,9 +929,16 @@ class DeviceTrajectory:
         return e.value, s.value
 
     def _need_basis(self):
+        """The transforms' mode on this trajectory's context, by quantization.use_streamed: above the resident limit
+        (N > 2048 by default) the blocks are rebuilt slab by slab for each call, else the basis is computed once."""
+        from .quantization import use_streamed, slab_bytes
+        if use_streamed(self.N):
+            _lib.check(self._lib.qf_basis_stream(self.ctx.handle, ctypes.c_longlong(slab_bytes())))
+            return
         if not getattr(self, "_basis_ready", False):
             _lib.check(self._lib.qf_basis_compute(self.ctx.handle))     # quantization.py:68-113, on the device
             self._basis_ready = True
+        _lib.check(self._lib.qf_basis_stream(self.ctx.handle, ctypes.c_longlong(0)))
 
     @classmethod
     def from_shr(cls, omega, N=-1, device=None):

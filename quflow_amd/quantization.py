@@ -7,17 +7,29 @@ argument meaning and conventions, so that initial data (`shr2mat(omega, N)`) and
 
 What runs where
   * the transforms -- one dense real (N-m)x(N-m) block of the basis times the m-th diagonal for
-    every m, i.e. an HBM-bound sweep over the N^3/3-entry basis -- are hand-written HIP kernels
-    behind the C ABI (qf_shr2mat / qf_mat2shr / qf_shc2mat / qf_mat2shc); the basis is uploaded
-    once per context and stays resident in HBM (2.9 GB at N=1024, 23 GB at N=2048);
+    every m -- are hand-written HIP kernels behind the C ABI (qf_shr2mat / qf_mat2shr /
+    qf_shc2mat / qf_mat2shc), on one of two paths:
+      - resident: the basis is uploaded once per context and stays in HBM (2.9 GB at N=1024,
+        23 GB at N=2048); a transform is an HBM-bound sweep over it;
+      - streamed (qf_basis_stream): no basis is stored.  Each call rebuilds the blocks it needs --
+        m < Nmax, columns j < Nmax - m -- into a slab of bounded size and applies them there,
+        slab after slab, with the same bits as the resident path.  Memory stays near N^2, so
+        N = 4096 and 8192 (183 GB and 1.5 TB of basis) transform, and a band-limited call
+        (n_omega = (lmax+1)^2) only builds about N Nmax^2 / 2 entries.
+    `streamed=None` (the default of every transform) picks the resident path when a basis for N
+    is already cached (`set_basis`, an earlier `get_basis`) or when it takes at most
+    QUFLOW_HIP_BASIS_RESIDENT_MB (32768) MiB -- every N <= 2048 -- and streams otherwise, in slabs of
+    QUFLOW_HIP_BASIS_SLAB_MB (4096) MiB; `streamed=True` / `False` force a path;
   * the basis itself (quantization.py:68-113: the eigenvectors of the tridiagonal blocks of the
     direct Laplacian, which the reference gets from LAPACK) is computed on the device as well
     (qf_basis_compute: the spectrum -el(el+1) is known, so each eigenvector is one twisted
-    factorisation); `set_basis` installs a basis loaded from a reference-written file instead.
+    factorisation); `set_basis` installs a basis loaded from a reference-written file instead,
+    which then takes the resident path.
 
 There is no CPU path for the transforms: without the library or a GPU they raise.
 """
 import ctypes
+import os
 import warnings
 
 import numpy as np
@@ -118,18 +130,49 @@ def set_basis(N, basis):
     return basis
 
 
+RESIDENT_MB = 32768     # QUFLOW_HIP_BASIS_RESIDENT_MB: the largest basis the automatic choice keeps resident
+SLAB_MB = 4096          # QUFLOW_HIP_BASIS_SLAB_MB: the slab budget of the streamed path
+
+
+def slab_bytes():
+    """The streamed path's slab budget in bytes (QUFLOW_HIP_BASIS_SLAB_MB MiB)."""
+    return int(float(os.environ.get("QUFLOW_HIP_BASIS_SLAB_MB", SLAB_MB)) * (1 << 20))
+
+
+def use_streamed(N, streamed=None):
+    """Whether a transform of size N streams the basis.  True / False force the path.  None: resident when a
+    basis for N is cached (`set_basis`, an earlier `get_basis`: that very basis is what the transforms use) or
+    when the basis takes at most QUFLOW_HIP_BASIS_RESIDENT_MB MiB; streamed otherwise."""
+    if streamed is not None:
+        return bool(streamed)
+    if (N, np.dtype(np.float64)) in _basis_cache:
+        return False
+    limit = float(os.environ.get("QUFLOW_HIP_BASIS_RESIDENT_MB", RESIDENT_MB)) * (1 << 20)
+    return basis_size(N) * 8 > limit
+
+
 def _resident_context(N, device=None):
-    """The context for N with the basis resident in HBM (uploaded once)."""
+    """The context for N with the basis resident in HBM (uploaded once), in resident mode."""
     ctx = get_context(N, device)
     basis = get_basis(N)
     key = (ctx.device, N)
     if _uploaded.get(key) != (id(basis), id(ctx)):
         _lib.check(ctx._lib.qf_basis_upload(ctx.handle, ptr(basis), ctypes.c_longlong(basis.shape[0])))
         _uploaded[key] = (id(basis), id(ctx))
+    _lib.check(ctx._lib.qf_basis_stream(ctx.handle, ctypes.c_longlong(0)))
     return ctx
 
 
-def shr2mat(omega, N=-1, berezin=False, device=None):
+def _transform_context(N, device=None, streamed=None):
+    """The context for N with its mode set for this call (use_streamed)."""
+    if not use_streamed(N, streamed):
+        return _resident_context(N, device)
+    ctx = get_context(N, device)
+    _lib.check(ctx._lib.qf_basis_stream(ctx.handle, ctypes.c_longlong(slab_bytes())))
+    return ctx
+
+
+def shr2mat(omega, N=-1, berezin=False, device=None, *, streamed=None):
     """Real spherical harmonics -> matrix, quflow/quantization.py:450-489."""
     omega = np.asarray(omega)
     assert np.isrealobj(omega), "omega must be a real array."
@@ -143,13 +186,13 @@ def shr2mat(omega, N=-1, berezin=False, device=None):
         omega[ind] /= bw[ind]
     out_dtype = np.complex64 if omega.dtype == np.float32 else np.complex128
     om = np.ascontiguousarray(omega, dtype=np.float64)
-    ctx = _resident_context(N, device)
+    ctx = _transform_context(N, device, streamed)
     W_out = np.zeros((N, N), dtype=np.complex128)
     _lib.check(ctx._lib.qf_shr2mat(ctx.handle, ptr(om), ctypes.c_longlong(om.shape[0]), ptr(W_out)))
     return W_out.astype(out_dtype, copy=False)
 
 
-def mat2shr(W, elmax=-1, berezin=False, device=None):
+def mat2shr(W, elmax=-1, berezin=False, device=None, *, streamed=None):
     """Matrix -> real spherical harmonics, quflow/quantization.py:492-525 (including its
     `elmax` convention: the output has ((elmax+1)^2)^2 entries)."""
     W = np.asarray(W)
@@ -161,7 +204,7 @@ def mat2shr(W, elmax=-1, berezin=False, device=None):
     out_dtype = np.float32 if W.dtype == np.complex64 else np.float64
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     omega = np.zeros(Nmax ** 2, dtype=np.float64)
-    ctx = _resident_context(N, device)
+    ctx = _transform_context(N, device, streamed)
     _lib.check(ctx._lib.qf_mat2shr(ctx.handle, ptr(Wc), ptr(omega), ctypes.c_longlong(omega.shape[0])))
     if berezin:      # quantization.py:514-517
         warnings.warn("Berezin scaling in mat2shr is ill adviced. Use in shr2fun instead (default).")
@@ -169,7 +212,7 @@ def mat2shr(W, elmax=-1, berezin=False, device=None):
     return omega.astype(out_dtype, copy=False)
 
 
-def shc2mat(omega, N=-1, berezin=False, device=None):
+def shc2mat(omega, N=-1, berezin=False, device=None, *, streamed=None):
     """Complex spherical harmonics -> matrix, quflow/quantization.py:528-566."""
     omega = np.asarray(omega)
     if N == -1:
@@ -186,19 +229,19 @@ def shc2mat(omega, N=-1, berezin=False, device=None):
         omega = np.array(omega, dtype=np.complex128)
         omega[ind] /= bw[ind]
     om = np.ascontiguousarray(omega, dtype=np.complex128)
-    ctx = _resident_context(N, device)
+    ctx = _transform_context(N, device, streamed)
     W_out = np.zeros((N, N), dtype=np.complex128)
     _lib.check(ctx._lib.qf_shc2mat(ctx.handle, ptr(om), ptr(W_out)))
     return W_out
 
 
-def mat2shc(W, berezin=False, device=None):
+def mat2shc(W, berezin=False, device=None, *, streamed=None):
     """Matrix -> complex spherical harmonics, quflow/quantization.py:569-592."""
     W = np.asarray(W)
     N = W.shape[0]
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     omega = np.zeros(N ** 2, dtype=np.complex128)
-    ctx = _resident_context(N, device)
+    ctx = _transform_context(N, device, streamed)
     _lib.check(ctx._lib.qf_mat2shc(ctx.handle, ptr(Wc), ptr(omega)))
     if berezin:      # quantization.py:578-581
         warnings.warn("Berezin scaling in mat2shc is ill adviced. Use in shc2fun instead (default).")
