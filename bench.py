@@ -19,17 +19,24 @@ the GPU, and fails if fewer than N devices are visible -- it never reports a 1-G
 The state is resident in HBM before the timed region starts; the timed region is
 bracketed by a barrier + device synchronisation on both sides.
 
+A plain run does only what the headline needs: set-up, the clock warm-up, the W warm-up
+steps, the K timed steps, --dump-outputs, the JSON line.  With --full (rank 0, --gpus 1)
+it then also takes every measurement of its own that follows -- `value_without_prewarm`,
+the instrumented pass, the fixed-iteration protocol, config 3, the other sizes, replicas
+per GPU, complex64, smooth data, the CPU baseline and the per-call timings.
+
 Extra objects on the JSON line:
   roofline     -- the dominant kernel (first product of the complex GEMM pair, fp64 MFMA):
                   algorithmic flops per launch (8 N^3) / mean launch duration measured
                   with HIP events on the launch stream during the timed region (`frac`), next to the
-                  flops the 3M kernel EXECUTES (6 N^3: `executed_frac`), the other two kernels of an
-                  iteration (instrumented pass after the timed region), the whole step against its
-                  bound (`whole_step`) and the fixed-iteration protocol of the reference's profiler.
-  cpu_baseline -- the CPU oracle (oracle/isomp_oracle.py: numpy zgemm + OpenMP Thomas),
-                  timed on this host's cores on a bounded sample of the same workload
+                  flops the 3M kernel EXECUTES (6 N^3: `executed_frac`); with --full also the other
+                  two kernels of an iteration (instrumented pass after the timed region), the whole
+                  step against its bound (`whole_step`) and the fixed-iteration protocol of the
+                  reference's profiler.
+  cpu_baseline -- with --full: the CPU oracle (oracle/isomp_oracle.py: numpy zgemm + OpenMP
+                  Thomas), timed on this host's cores on a bounded sample of the same workload
                   (rank 0, --gpus 1 only).  The oracle is the checker/baseline, never the
-                  thing measured as `value`.
+                  thing measured as `value`.  None in a plain run.
 """
 import argparse
 import ctypes
@@ -115,18 +122,23 @@ def parse(argv=None):
                     help="c128: the headline (complex128 state, fp64 arithmetic).  c64: a complex64 state advanced in "
                          "single precision as the reference does with complex64 input (float32 Poisson solve, complex64 "
                          "products on the fp32 matrix cores, roofline against the 157.3 TFLOP/s fp32 MFMA peak)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every side measurement (single GPU): the run without the clock warm-up, "
+                         "the instrumented pass and the fixed-iteration protocol, config 3, the other sizes, replicas "
+                         "per GPU, complex64, smooth data, the CPU baseline and the per-call timings.  Off: the run "
+                         "does only what its headline needs")
     ap.add_argument("--no-config3", action="store_true",
-                    help="skip the short int8-products side measurement the default single-GPU run appends")
+                    help="with --full: skip the short int8-products side measurement it appends")
     ap.add_argument("--no-per-call", action="store_true",
-                    help="skip the per-call timings of the public host-array API (solve_poisson / laplace / commutator)")
+                    help="with --full: skip the per-call timings of the public host-array API (solve_poisson / laplace / commutator)")
     ap.add_argument("--no-side-runs", action="store_true",
-                    help="skip the instrumented pass, the fixed-iteration protocol and the other sizes")
+                    help="with --full: skip the instrumented pass, the fixed-iteration protocol and the other sizes")
     ap.add_argument("--prewarm-ms", type=float, default=150.0,
                     help="GPU clock warm-up before the W warm-up steps: a scratch trajectory of the same workload "
                          "is advanced for this long (a fresh process finds the GPU idle; its clock takes ~100 ms of "
                          "load to come up).  0 disables")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget; 0 disables")
-    ap.add_argument("--cpu-cores", type=int, default=16, help="threads for the CPU baseline (BLAS + OpenMP)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: CPU baseline budget; 0 disables")
+    ap.add_argument("--cpu-cores", type=int, default=16, help="with --full: threads for the CPU baseline (BLAS + OpenMP)")
     ap.add_argument("--no-kernel-events", action="store_true", help="no per-launch HIP events in the timed region")
     ap.add_argument("--kernel-table", action="store_true",
                     help="HIP events around every hot-path launch; per-kernel table on stderr (diagnostic)")
@@ -963,7 +975,7 @@ def main():
     if args.prewarm_ms > 0 and args.stepper == "isomp" and injected is None:
         # clock warm-up on a scratch trajectory (not the measured state, not counted in W or K)
         scratch = qfa.DeviceTrajectory(W0, device=device_index)
-        if world == 1 and not c64:
+        if world == 1 and not c64 and args.full:
             # the same measurement WITHOUT the clock warm-up, taken first (a fresh process, an idle GPU): W warm-up
             # steps, then K timed steps with the chunk's diagnostics, on the scratch trajectory.  Reported beside
             # `value` as config.value_without_prewarm; it also is the first part of the warm-up of what follows.
@@ -1182,7 +1194,7 @@ def main():
                                "note": "frac = flops the kernel executes (6 N^3: 3M complex product) / launch time / peak: the share "
                                        "of the matrix pipe it keeps busy; algorithmic_frac prices the 8 N^3 of a complex product "
                                        "(SURVEY.md 8d) and may exceed 1"}
-            if (world == 1 and args.stepper == "isomp" and not args.no_side_runs and not args.kernel_table):
+            if (world == 1 and args.full and args.stepper == "isomp" and not args.no_side_runs and not args.kernel_table):
                 # second product and Laplacian inverse: events around every launch, outside the timed region
                 times, st2, plan2 = instrumented_pass(qfa, _lib, W0, dt, min(args.steps, 50), kw, device_index)
                 a1, a2, a0 = times["gemm1"]["avg_s"], times["gemm2"]["avg_s"], times["poisson"]["avg_s"]
@@ -1231,7 +1243,7 @@ def main():
                     out["roofline"]["fixed_iterations_10"] = fixed_iteration_run(qfa, _lib, W0, N, device_index)
         else:
             out["roofline"] = None
-        if (world == 1 and args.products == "f64" and args.stepper == "isomp" and not args.no_config3
+        if (world == 1 and args.full and args.products == "f64" and args.stepper == "isomp" and not args.no_config3
                 and injected is None and N % 64 == 0 and N >= 256):
             # BASELINE.json config 3: the low-precision-MFMA commutator = six int8 digits
             # (round 4: six digits for the first product, five for the second -- `i8x65`; the six-and-six form of
@@ -1259,7 +1271,7 @@ def main():
                                           "N512": complex64_side_run(args, qfa, 512, 400, 20, device_index)}
                 # smooth initial data (IC-B: ~7 iterations per step instead of ~2), headline size
                 out["smooth_data"] = {"N1024": smooth_data_side_run(args, qfa, 1024, 100, 10, device_index)}
-        if world == 1 and args.cpu_seconds > 0 and injected is None:
+        if world == 1 and args.full and args.cpu_seconds > 0 and injected is None:
             out["cpu_baseline"] = cpu_baseline(args, dt)
             for key, n_side in (("N512", 512), ("N2048", 2048)):
                 if key in (out.get("other_sizes") or {}):      # bounded: <= 3 s of CPU work each (+ one warm-up step)

@@ -1,10 +1,13 @@
 """bench.py's own launch path (`python bench.py --gpus N` without torch.distributed.run) and its
 gather report, on CPU: two ranks, gloo instead of RCCL, and a trajectory injected from the CPU oracle
-(tests only -- a measurement never sets QUFLOW_BENCH_TRAJECTORY; the line then says so in `data`)."""
+(tests only -- a measurement never sets QUFLOW_BENCH_TRAJECTORY; the line then says so in `data`).  One GPU test:
+what a plain run leaves out and --full adds."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 from conftest import REPO
 
@@ -273,3 +276,52 @@ def test_dump_outputs_samples_a_state_above_the_budget(tmp_path, monkeypatch):
     np.testing.assert_array_equal(np.load(tmp_path / "a" / "W_real.npy"), flat.real)
     np.testing.assert_array_equal(np.load(tmp_path / "a" / "W_imag.npy"), flat.imag)
     assert np.load(tmp_path / "a" / "iterations.npy").tolist() == [2.5]
+
+
+def test_full_runs_the_same_timed_steps_and_prints_the_same_line_form(tmp_path, oracle):
+    """--full only adds measurements after the headline: the trajectory sees the same calls (W warm-up steps, then the K
+    timed steps), the dumped state is the same, and the line has the same keys as a plain run's."""
+    import numpy as np
+    lines, calls, dumps = {}, {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        calls[mode] = tmp_path / ("calls_%s.txt" % mode)
+        out = tmp_path / ("out_%s" % mode)
+        res = run_bench(tmp_path, ["--steps", "3", "--warmup", "2", "--N", "16", "--cpu-seconds", "0", "--dump-outputs", str(out)]
+                        + extra, QF_TRAJ_CALLS=str(calls[mode]))
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines[mode] = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])
+        dumps[mode] = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert calls["plain"].read_text().split() == calls["full"].read_text().split() == ["2", "3"]
+    a, b = lines["plain"], lines["full"]
+    assert sorted(a) == sorted(b) and sorted(a["config"]) == sorted(b["config"])
+    assert a["steps"] == b["steps"] == 3 and a["warmup"] == b["warmup"] == 2
+    assert dumps["plain"].keys() == dumps["full"].keys()
+    for f in dumps["plain"]:
+        np.testing.assert_array_equal(dumps["plain"][f], dumps["full"][f], err_msg=f)
+
+
+@pytest.mark.gpu
+def test_plain_run_leaves_the_side_measurements_to_full(tmp_path):
+    """A plain run measures the headline and nothing else: no run without the clock warm-up, no instrumented pass, no
+    config 3, no CPU baseline -- while the roofline of the timed region's own events stays on its line.  --full adds
+    them all back."""
+    base = {k: v for k, v in os.environ.items()
+            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID",
+                         "QUFLOW_BENCH_TRAJECTORY", "QUFLOW_BENCH_BACKEND")}
+    args = ["--gpus", "1", "--steps", "8", "--warmup", "2", "--N", "512", "--cpu-seconds", "0.5"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args + extra, env=base, capture_output=True,
+                           text=True, timeout=600, cwd=REPO)
+        assert r.returncode == 0, (mode, r.stderr[-3000:])
+        lines[mode] = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+    a, b = lines["plain"], lines["full"]
+    for d in (a, b):
+        assert d["value"] > 0 and d["n_gpus"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert d["roofline"]["frac"] > 0 and d["roofline"]["launches_timed_with_events"] > 0
+    assert a["config"]["value_without_prewarm"] is None and a["cpu_baseline"] is None
+    assert not {"second_product", "laplacian_inverse", "whole_step", "fixed_iterations_10"} & set(a["roofline"])
+    assert "config3_lowprecision_products" not in a
+    assert b["config"]["value_without_prewarm"] > 0 and b["cpu_baseline"]["value"] > 0
+    assert {"second_product", "laplacian_inverse", "whole_step", "fixed_iterations_10"} <= set(b["roofline"])
+    assert b["config3_lowprecision_products"]["value"] > 0
