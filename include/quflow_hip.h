@@ -283,6 +283,15 @@ int qf_mat2shc(qf_ctx *ctx, const void *W_host, void *omega_host);
 int qf_shr2fun(qf_ctx *ctx, const double *omega_host, long long n_omega, int L, int berezin, double *f_host);
 /* omega: n_omega complex128; isreal: f_host is double (L, 2L-1) (the m >= 0 half of omega, a real map), else complex128 */
 int qf_shc2fun(qf_ctx *ctx, const void *omega_host, long long n_omega, int L, int berezin, int isreal, void *f_host);
+/* fun2shc / fun2shr (quflow/transforms.py:189-217, 404-419): McEwen-Wiaux analysis of the MW grid f (L, 2L-1), row-major,
+ * double when isreal != 0, else complex128; 1 <= L <= 8192, independent of ctx->N, no quantization basis needed.
+ * qf_fun2shc writes L^2 complex128 (index l^2 + l + m), qf_fun2shr the L^2 doubles shc2shr makes of them.  The inverse of
+ * qf_shc2fun / qf_shr2fun with berezin == 0 on band-limited grids.  Two real L x L operators that depend on L only are
+ * built on the first call at a bandwidth and kept on ctx until another bandwidth is asked for.
+ * qf_fun2shr with omega_host == NULL leaves the coefficients in the device copy that qf_shr2mat(ctx, NULL, L*L, ...) and
+ * qf_shr2fun(ctx, NULL, ...) read; that form needs L <= ctx->N. */
+int qf_fun2shc(qf_ctx *ctx, const void *f_host, int L, int isreal, void *omega_host);
+int qf_fun2shr(qf_ctx *ctx, const void *f_host, int L, int isreal, double *omega_host);
 
 /* ---- diagnostics on the ctx state W: quflow/physics.py:26-38 with
  *      inner_L2 (quflow/geometry.py:72-76) -------------------------------------- */

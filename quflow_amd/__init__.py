@@ -20,6 +20,8 @@ from . import geometry
 from . import ensemble
 from . import quantization
 from . import transforms
+from . import sht
+from . import analysis
 from . import simulation
 from .simulation import Simulation, solve, create_runfile
 QuSimulation = Simulation          # the reference's name (quflow/simulation.py:60): scripts that say qf.QuSimulation run unchanged

@@ -125,6 +125,8 @@ SIGNATURES = {
     "qf_mat2shc": (ctypes.c_int, [_vp, _vp, _vp]),
     "qf_shr2fun": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_shc2fun": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "qf_fun2shc": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "qf_fun2shr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_diagnostics": (ctypes.c_int, [_vp, _dp, _dp]),
     "qf_norm_inf_W": (ctypes.c_int, [_vp, _dp]),
     "qf_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -221,7 +221,7 @@ int qf_ctx_destroy(qf_ctx *ctx)
                     ctx->t32_partial, ctx->t32_arrive, ctx->W2, ctx->Whalf2, ctx->ns_inv, ctx->ns_tmp, ctx->multi_rowpart, ctx->scalars, ctx->sk_partial, ctx->sk_flags, ctx->basis, ctx->sh_stage, ctx->sh_omega, ctx->slab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    void *sht[] = {ctx->sht.omega, ctx->sht.tab, ctx->sht.col, ctx->sht.At, ctx->sht.tw, ctx->sht.f};
+    void *sht[] = {ctx->sht.omega, ctx->sht.tab, ctx->sht.col, ctx->sht.At, ctx->sht.tw, ctx->sht.f, ctx->sht.H, ctx->sht.Q};
     for (void *p : sht)
         if (p) (void)hipFree(p);
     for (cplx *p : ctx->multi)

@@ -240,17 +240,20 @@ static int sht_args(const char *who, long long n_omega, int L, const void *f_hos
 }
 
 // ctx->sht grown to what (L, isreal) needs; a buffer that is too small is replaced (hipFree waits for the device)
-static int sht_reserve(qf_ctx *ctx, int L, int isreal)
+static int sht_reserve(qf_ctx *ctx, int L, int isreal, bool analysis = false)
 {
-    size_t want[6];
-    qf_sht_sizes(L, isreal, want);
+    size_t want[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (analysis) qf_sht_analysis_sizes(L, isreal, want);
+    else qf_sht_sizes(L, isreal, want);
     qf_sht &S = ctx->sht;
-    void **bufs[6] = {(void **)&S.omega, (void **)&S.tab, (void **)&S.col, (void **)&S.At, (void **)&S.tw, (void **)&S.f};
-    for (int i = 0; i < 6; ++i) {
+    void **bufs[8] = {(void **)&S.omega, (void **)&S.tab, (void **)&S.col, (void **)&S.At, (void **)&S.tw, (void **)&S.f,
+                      (void **)&S.H, (void **)&S.Q};
+    for (int i = 0; i < 8; ++i) {
         if (want[i] <= S.cap[i]) continue;
         if (*bufs[i]) (void)hipFree(*bufs[i]);
         *bufs[i] = nullptr;
         S.cap[i] = 0;
+        if (i == 7) S.q_L = 0;
         QF_HIP(hipMalloc(bufs[i], want[i]));
         S.cap[i] = want[i];
     }
@@ -330,6 +333,60 @@ int qf_shc2fun(qf_ctx *ctx, const void *omega_host, long long n_omega, int L, in
     }
     const long long n = std::min(n_omega, (long long)L * L);
     return sht_run(ctx, omega_host, nullptr, n, L, berezin, 0, isreal ? 1 : 0, f_host);
+}
+
+// ---- spherical-harmonic analysis (quflow/transforms.py:189-217, 404-419; kernels in sht.hip) ------------------
+// f_host (L, 2L-1) -> L^2 coefficients: real (shr) or complex.  out_dev == NULL: into ctx->sht.omega; the result goes to
+// omega_host when that is given.  Q_even / Q_odd are rebuilt when the bandwidth differs from the one they were made for.
+static int sht_analyse(qf_ctx *ctx, const char *who, const void *f_host, int L, int isreal, int shr, double *out_dev,
+                       void *omega_host)
+{
+    if (L < 1 || L > 8192) {
+        qf_set_error("%s: bandwidth L=%d is outside 1..8192", who, L);
+        return QF_ERR_INVALID;
+    }
+    if (!f_host) {
+        qf_set_error("%s: null grid", who);
+        return QF_ERR_INVALID;
+    }
+    QF_TRY(sht_reserve(ctx, L, isreal, true));
+    QF_TRY(sht_tables(ctx, L, 0));
+    if (ctx->sht.q_L != L) QF_TRY(qf_launch_sht_qbuild(ctx, L));     // (uses f as workspace: before the upload)
+    const size_t LL = (size_t)L * L;
+    QF_HIP(hipMemcpyAsync(ctx->sht.f, f_host, (size_t)L * (2 * (size_t)L - 1) * (isreal ? sizeof(double) : sizeof(cplx)),
+                          hipMemcpyHostToDevice, ctx->stream));
+    if (!out_dev) out_dev = ctx->sht.omega;
+    QF_TRY(qf_launch_sht_analysis(ctx, L, shr, isreal, out_dev));
+    if (omega_host)
+        QF_HIP(hipMemcpyAsync(omega_host, out_dev, LL * (shr ? sizeof(double) : sizeof(cplx)), hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
+int qf_fun2shc(qf_ctx *ctx, const void *f_host, int L, int isreal, void *omega_host)
+{
+    QF_TRY(check_ctx(ctx));
+    if (!omega_host) {
+        qf_set_error("qf_fun2shc: null coefficient array");
+        return QF_ERR_INVALID;
+    }
+    return sht_analyse(ctx, "qf_fun2shc", f_host, L, isreal ? 1 : 0, 0, nullptr, omega_host);
+}
+
+int qf_fun2shr(qf_ctx *ctx, const void *f_host, int L, int isreal, double *omega_host)
+{
+    QF_TRY(check_ctx(ctx));
+    if (omega_host) return sht_analyse(ctx, "qf_fun2shr", f_host, L, isreal ? 1 : 0, 1, nullptr, omega_host);
+    // omega_host == NULL: the coefficients stay in ctx->sh_omega, where qf_shr2mat(NULL) and qf_shr2fun(NULL) read them
+    if (L > ctx->N) {
+        qf_set_error("qf_fun2shr: omega == NULL keeps L^2 coefficients on a context of N^2: L=%d exceeds N=%d", L, ctx->N);
+        return QF_ERR_INVALID;
+    }
+    QF_TRY(alloc_stage(ctx));
+    ctx->sh_shr_count = 0;
+    QF_TRY(sht_analyse(ctx, "qf_fun2shr", f_host, L, isreal ? 1 : 0, 1, ctx->sh_omega, nullptr));
+    ctx->sh_shr_count = (long long)L * L;
+    return QF_OK;
 }
 
 

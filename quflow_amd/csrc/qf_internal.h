@@ -266,8 +266,9 @@ struct qf_event_pair {
     int kernel_id;
 };
 
-// Scratch of the spherical-harmonic synthesis (sht.hip, qf_shr2fun / qf_shc2fun): allocated on first use, grown with the
-// bandwidth L (never shrunk), freed with the context.  `cap` holds the bytes each buffer has.
+// Scratch of the spherical-harmonic synthesis and analysis (sht.hip, qf_shr2fun / qf_shc2fun / qf_fun2shr / qf_fun2shc):
+// allocated on first use, grown with the bandwidth L (never shrunk), freed with the context.  `cap` holds the bytes each
+// buffer has.
 struct qf_sht {
     double *omega = nullptr;     // coefficients uploaded from the host (min(n_omega, L^2) entries, real or complex)
     double *tab = nullptr;       // 2 L doubles: sqrt(4 pi) w_l, then the seeds lambda_mm / sin^m (host-made, long double)
@@ -275,7 +276,10 @@ struct qf_sht {
     double *At = nullptr;        // Kpad x ldA doubles: the Legendre stage's output, [k = 2m + (re, im)][ring]
     double2 *tw = nullptr;       // 2L - 1 twiddles (cos, sin)(2 pi k / (2L - 1))
     double *f = nullptr;         // the grid, (L, 2L-1) doubles or complex
-    size_t cap[6] = {0, 0, 0, 0, 0, 0};
+    double *H = nullptr;         // analysis: the theta operator's output, laid out as At
+    double *Q = nullptr;         // analysis: Q_even, Q_odd for the bandwidth q_L, each padded to a multiple of 64 squared
+    int q_L = 0;                 // 0: Q holds nothing
+    size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 struct qf_ctx {
@@ -541,6 +545,12 @@ int qf_launch_mat2shc(qf_ctx *ctx, const cplx *W_dev, double *omega_dev);
 // filled; result in ctx->sht.f: (L, 2L-1) doubles when isreal, complex128 otherwise.
 int qf_launch_sht_synth(qf_ctx *ctx, int L, int shr, int isreal, const double *omega_dev, long long n_valid);
 void qf_sht_sizes(int L, int isreal, size_t bytes[6]);   // what each ctx->sht buffer needs for (L, isreal)
+// analysis: the grid in ctx->sht.f (uploaded by the caller) -> L^2 coefficients in omega_dev, real (shr != 0: fun2shr) or
+// complex (fun2shc); needs ctx->sht.tab filled and ctx->sht.Q built for this L (qf_launch_sht_qbuild, which uses f and H
+// as its workspace: build before the grid is uploaded).
+int qf_launch_sht_analysis(qf_ctx *ctx, int L, int shr, int isreal, double *omega_dev);
+int qf_launch_sht_qbuild(qf_ctx *ctx, int L);
+void qf_sht_analysis_sizes(int L, int isreal, size_t bytes[8]);   // as qf_sht_sizes; [6] = H, [7] = Q
 
 // ---- ozaki.hip: complex products on the int8 matrix cores from digit-sliced operands
 struct qf_oz_job {

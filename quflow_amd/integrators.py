@@ -957,6 +957,31 @@ class DeviceTrajectory:
         _lib.check(self._lib.qf_shr2mat(self.ctx.handle, ptr(omega), ctypes.c_longlong(omega.shape[0]), None))
         return self
 
+    @classmethod
+    def from_fun(cls, f, N=-1, device=None):
+        """Start a trajectory from a real function on the MW grid (L, 2L-1): W0 = shr2mat(sht.fun2shr(f), N) built
+        straight into the resident state.  Only the grid crosses PCIe: the analysis leaves its L^2 coefficients on the
+        device, where shr2mat reads them.  N = -1 means N = L; L < N band-limits as shr2mat does for a short omega; L > N
+        is refused.  The trajectory is then the one from_shr(sht.fun2shr(f), N) gives, bit for bit."""
+        from .sht import _grid
+        f, L, isreal = _grid(f)
+        assert isreal, "f must be a real array."
+        if N == -1:
+            N = L
+        N = int(N)
+        if L > N:
+            raise ValueError("from_fun: the grid's bandwidth L=%d exceeds the matrix size N=%d" % (L, N))
+        self = cls.__new__(cls)
+        self.N = N
+        self.c64 = False
+        self.dtype = np.complex128
+        self.ctx = Context(self.N, default_device() if device is None else device)
+        self._lib = self.ctx._lib
+        self._need_basis()
+        _lib.check(self._lib.qf_fun2shr(self.ctx.handle, ptr(f), L, 1, None))
+        _lib.check(self._lib.qf_shr2mat(self.ctx.handle, None, ctypes.c_longlong(L * L), None))
+        return self
+
     def shr(self, n_omega=None):
         """mat2shr of the resident state (quflow/quantization.py:492-525): what simulation.py:287-344
         stores for an 'shr' output -- N^2 doubles cross PCIe instead of the N^2 complex state."""

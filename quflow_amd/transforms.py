@@ -7,8 +7,9 @@ Mirrors `quflow.transforms` (quflow/transforms.py) with the reference's names an
   * `as_fun`, `as_shr` -- the reference's dispatch on the kind of data;
   * `shr2shc`, `shc2shr`, `sphgrid`, `fun2img`, `img2fun` -- host numpy, as in the reference (vectorised).
 
-Not implemented: the analysis direction `fun2shc` / `fun2shr` (MW analysis is a different algorithm); both raise
-NotImplementedError.  There is no CPU path for the synthesis: without the library or a GPU it raises.
+The analysis direction `fun2shc` / `fun2shr` (and `as_shr` of a function or an image) lives in `quflow_amd.sht`; the
+three names here still raise NotImplementedError.  There is no CPU path for the synthesis: without the library or a GPU
+it raises.
 """
 import ctypes
 from math import isqrt
