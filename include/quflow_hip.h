@@ -45,6 +45,7 @@ extern "C" {
                              * into W): the state is left as it was after the last completed step, as the reference's array is.
                              * (Residual entries above 1.3e154 count as non-finite here -- their squares overflow --, the
                              * reference's scaled abs() gives up at 1.8e308.) */
+#define QF_ERR_NOCONVERGE 8 /* qf_eigh and its kin: the sweep cap was reached before every pair of vectors was orthogonal */
 
 #define QF_VERSION 100      /* 0.1.0, tracks quflow.__version__ (quflow/__init__.py:18) */
 
@@ -303,6 +304,29 @@ int qf_isomp_diag(qf_ctx *ctx, double dt, int steps, double tol, int minit, int 
                   int reinitialize, qf_isomp_stats *stats, double *energy_euler, double *enstrophy);
 /* matrix infinity norm of the state, np.linalg.norm(W, inf) (isospectral.py:448) */
 int qf_norm_inf_W(qf_ctx *ctx, double *out);
+
+/* ---- Hermitian eigendecomposition H = V diag(lambda) V^H on the device (csrc/eigh.hip): parallel one-sided Jacobi on
+ *      H + 2 |H|_inf I, eigenvalues refined by their Rayleigh quotients with H.  complex128 only.  lambda: N doubles,
+ *      ascending; V: (N,N) complex128, unitary, column j belongs to lambda[j].  Deterministic: two calls return the same
+ *      bits, and lambda has the same bits with and without V.  An inf or NaN entry: QF_ERR_NONFINITE; the sweep cap (60)
+ *      reached: QF_ERR_NOCONVERGE.  The work matrices (3 N^2 complex128) are allocated on the context's first such call
+ *      and freed with it.  (The reference calls LAPACK through numpy: np.linalg.eig in quflow/analysis.py:28.) -------- */
+typedef struct qf_eigh_stats {
+    int sweeps;               /* sweeps run, the last one (which rotated nothing) included; 0 for H = 0 */
+    long long rotations;      /* rotations applied */
+    double off;               /* the last sweep's worst |g_p^H g_q| / (|g_p| |g_q|) */
+} qf_eigh_stats;
+/* H_host: Hermitian (N,N).  V_host may be NULL (eigenvalues only); stats may be NULL. */
+int qf_eigh(qf_ctx *ctx, const void *H_host, double *lambda_host, void *V_host, qf_eigh_stats *stats);
+/* W_host: skew-Hermitian (N,N).  Decomposes -i W, formed on the device: W = V diag(i lambda) V^H. */
+int qf_eigh_skew(qf_ctx *ctx, const void *W_host, double *lambda_host, void *V_host, qf_eigh_stats *stats);
+/* The same for the context's resident state W: the invariant of the isospectral flow.  Only lambda crosses the bus. */
+int qf_eigh_state(qf_ctx *ctx, double *lambda_host, qf_eigh_stats *stats);
+/* scale_decomposition(W, P) of quflow/analysis.py:8-34 for a skew-Hermitian stream matrix P: with V the eigenvectors of
+ * -i P, Ws = V diag(diag(V^H W V)) V^H (the part of W that commutes with P) and Wr = W - Ws, all on the device.
+ * W_host == NULL: the context's resident state.  P_host == NULL: P = Delta^-1 W by the context's own solver
+ * (skew-Hermitian form).  Ws_host, Wr_host: (N,N) complex128 each. */
+int qf_scale_decomposition(qf_ctx *ctx, const void *W_host, const void *P_host, void *Ws_host, void *Wr_host);
 
 /* ---- measurement support (bench.py): HIP-event timing on the ctx stream -------- */
 #define QF_KERNEL_POISSON 0

@@ -22,6 +22,7 @@ from . import quantization
 from . import transforms
 from . import sht
 from . import analysis
+from . import linalg
 from . import simulation
 from .simulation import Simulation, solve, create_runfile
 QuSimulation = Simulation          # the reference's name (quflow/simulation.py:60): scripts that say qf.QuSimulation run unchanged
@@ -35,6 +36,7 @@ from .laplacian import (solve_poisson, laplace, PoissonHIP, solve_heat, solve_he
 from .integrators import (isomp, isomp_fixedpoint, IsompHIP, DeviceTrajectory, DeviceEnsemble, euler, heun, rk4,
                           isomp_simple, isomp_quasinewton, magmp, magmp_fixedpoint, solve_mhd,
                           commutator, commutator_generic, commutator_skewherm, estimate_stepsize, project_skewherm)
+from .analysis import scale_decomposition
 from .physics import energy_euler, enstrophy, inner_Hm1, norm_Hm1, inner_H1, norm_H1
 from .context import get_context, set_device, release_contexts, guard_report
 from ._lib import QuflowHipError, device_count, device_info

@@ -17,8 +17,9 @@ LIB_PATH = os.environ.get("QUFLOW_HIP_LIB") or os.path.join(_HERE, "libquflow_hi
 
 QF_OK = 0
 QF_ERR_NONFINITE = 7
+QF_ERR_NOCONVERGE = 8
 ERR_NAMES = {1: "QF_ERR_INVALID", 2: "QF_ERR_NO_DEVICE", 3: "QF_ERR_HIP", 4: "QF_ERR_STATE", 5: "QF_ERR_CALLBACK",
-             6: "QF_ERR_UNSUPPORTED", 7: "QF_ERR_NONFINITE"}
+             6: "QF_ERR_UNSUPPORTED", 7: "QF_ERR_NONFINITE", 8: "QF_ERR_NOCONVERGE"}
 
 KERNEL_IDS = {"poisson": 0, "gemm1": 1, "gemm2": 2, "norm": 3, "update": 4, "slice": 5}
 ERK_METHODS = {"euler": 0, "heun": 1, "rk4": 2}
@@ -59,6 +60,12 @@ class IsompStats(ctypes.Structure):
                 ("number_of_maxit", ctypes.c_longlong),
                 ("tol_used", ctypes.c_double),
                 ("last_resnorm", ctypes.c_double)]
+
+
+class EighStats(ctypes.Structure):
+    _fields_ = [("sweeps", ctypes.c_int),
+                ("rotations", ctypes.c_longlong),
+                ("off", ctypes.c_double)]
 
 
 # every symbol include/quflow_hip.h declares: (restype, argtypes)
@@ -129,6 +136,10 @@ SIGNATURES = {
     "qf_fun2shr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_diagnostics": (ctypes.c_int, [_vp, _dp, _dp]),
     "qf_norm_inf_W": (ctypes.c_int, [_vp, _dp]),
+    "qf_eigh": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(EighStats)]),
+    "qf_eigh_skew": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(EighStats)]),
+    "qf_eigh_state": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(EighStats)]),
+    "qf_scale_decomposition": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "qf_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "qf_profile_reset": (ctypes.c_int, [_vp]),
     "qf_profile_read": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), _dp]),
@@ -186,6 +197,15 @@ def check(rc):
         # QF_ERR_NONFINITE: the residual of a stepper's exit test is inf / NaN -- exactly where the reference's
         # scipy.linalg.norm(..., ord=inf) raises (isospectral.py:534, check_finite), with its message
         raise ValueError("array must not contain infs or NaNs")
+    if rc != QF_OK:
+        msg = load().qf_last_error()
+        raise QuflowHipError("%s: %s" % (ERR_NAMES.get(rc, "error %d" % rc),
+                                         msg.decode("utf-8", "replace") if msg else ""))
+
+
+def check_eigh(rc):
+    """`check` for the eigensolver's entry points: there QF_ERR_NONFINITE is an inf / NaN entry of the INPUT, not a stepper's
+    residual, and is reported as the library's own error with its message."""
     if rc != QF_OK:
         msg = load().qf_last_error()
         raise QuflowHipError("%s: %s" % (ERR_NAMES.get(rc, "error %d" % rc),

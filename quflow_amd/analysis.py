@@ -1,17 +1,62 @@
-"""Spectra and random initial data, quflow.analysis on top of the device transforms.
+"""Scale separation, spectra and random initial data: quflow.analysis on top of the device kernels.
 
-Mirrors quflow/analysis.py:37-148: `energy_spectrum`, `enstrophy_spectrum`, `random_shr`, `gamma_ratio`, with the
-reference's names, arguments and operations (its loops over degrees vectorised).  The data goes to real coefficients
-through `quflow_amd.sht.as_shr` -- a matrix through mat2shr, a function or an image through the device analysis fun2shr --
-and the sums over each degree are host numpy.
+Mirrors quflow/analysis.py: `scale_decomposition` (:8-34) and `energy_spectrum`, `enstrophy_spectrum`, `random_shr`,
+`gamma_ratio` (:37-148), with the reference's names, arguments and operations (its loops over degrees vectorised).
 
-Not here: `scale_decomposition` (quflow/analysis.py:8-34) needs a dense non-Hermitian eigensolver, which this package
-does not have.
+For the spectra the data goes to real coefficients through `quflow_amd.sht.as_shr` -- a matrix through mat2shr, a function
+or an image through the device analysis fun2shr -- and the sums over each degree are host numpy.
+
+`scale_decomposition` runs on the device from end to end (qf_scale_decomposition): the eigenvectors V of the stream matrix
+by the Hermitian eigensolver of `quflow_amd.linalg` applied to -i P, then Ws = V diag(diag(V^H W V)) V^H and Wr = W - Ws.
+The reference calls the general `np.linalg.eig`; this package has a Hermitian solver only, which covers every stream
+matrix of a skew-Hermitian state: a P that is not skew-Hermitian is refused (NotImplementedError), never sent to a CPU.
 """
+import ctypes
+
 import numpy as np
 
+from . import _lib
+from . import laplacian as _laplacian
+from .laplacian import solve_poisson
 from .quantization import mat2shr, ind2elm
 from .sht import as_shr
+
+
+def scale_decomposition(W, P=None, hamiltonian=solve_poisson):
+    """(Ws, Wr): the canonical scale separation of the vorticity matrix W (quflow/analysis.py:8-34).  Ws is the part of W
+    that commutes with the stream matrix P -- W in P's eigenbasis with the off-diagonal dropped -- and Wr = W - Ws.
+
+    P is computed when not given: the built-in `solve_poisson` (ours, a PoissonHIP or the reference's) on the device
+    inside the same call, any other `hamiltonian` by calling it on the host.  P must be skew-Hermitian."""
+    from .context import as_c128, get_context, ptr
+    from .integrators import _is_native_hamiltonian
+    Wa = np.asarray(W)
+    if Wa.dtype == np.complex64:
+        raise NotImplementedError("scale_decomposition of a complex64 W: the eigensolver is double only; convert to "
+                                  "complex128")
+    Wc = as_c128(Wa, "W")
+    N = Wc.shape[0]
+    if P is None and not (_is_native_hamiltonian(hamiltonian) and _laplacian._SKEW_HERM_):
+        # (the device's own solve is the skew-Hermitian form; after select_skewherm(False) the general one is asked for)
+        P = (solve_poisson if hamiltonian is None else hamiltonian)(W)
+    Pc = None
+    if P is not None:
+        Pc = as_c128(P, "P")
+        if Pc.shape != Wc.shape:
+            raise ValueError("W and P differ in shape: %s and %s" % (Wc.shape, Pc.shape))
+        defect = np.abs(Pc + Pc.conj().T)
+        if np.any(defect > N * np.finfo(np.float64).eps * np.abs(Pc).max()):
+            raise NotImplementedError("scale_decomposition needs a skew-Hermitian stream matrix P (max|P + P^H| = %.3g): "
+                                      "this package has a Hermitian eigensolver only, no general one and no CPU fallback"
+                                      % defect.max())
+    if N == 1:          # (no context that small; every 1 x 1 matrix commutes with P)
+        return Wc.copy(), np.zeros_like(Wc)
+    Ws = np.empty_like(Wc)
+    Wr = np.empty_like(Wc)
+    ctx = get_context(N)
+    _lib.check_eigh(ctx._lib.qf_scale_decomposition(ctx.handle, ptr(Wc), ptr(Pc) if Pc is not None else None,
+                                                    ptr(Ws), ptr(Wr)))
+    return Ws, Wr
 
 
 def _degree_sums(omegar):

@@ -224,6 +224,9 @@ int qf_ctx_destroy(qf_ctx *ctx)
     void *sht[] = {ctx->sht.omega, ctx->sht.tab, ctx->sht.col, ctx->sht.At, ctx->sht.tw, ctx->sht.f, ctx->sht.H, ctx->sht.Q};
     for (void *p : sht)
         if (p) (void)hipFree(p);
+    void *eigh[] = {ctx->eigh.H, ctx->eigh.G, ctx->eigh.V, ctx->eigh.ray, ctx->eigh.sig, ctx->eigh.perm, ctx->eigh.word};
+    for (void *p : eigh)
+        if (p) (void)hipFree(p);
     for (cplx *p : ctx->multi)
         if (p) (void)hipFree(p);
     for (int q = 0; q < 4; ++q) {

@@ -282,6 +282,17 @@ struct qf_sht {
     size_t cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// Work set of the Hermitian eigensolver (eigh.hip, api_eigh.hip): allocated on first use, freed with the context.
+struct qf_eigh_ws {
+    cplx *H = nullptr;           // the matrix that is decomposed (kept for the Rayleigh quotients)
+    cplx *G = nullptr;           // the rotated rows; on exit V^H, rows in the order the sweeps left them
+    cplx *V = nullptr;           // product scratch, then V with its columns sorted
+    cplx *ray = nullptr;         // N complex: row dots (Rayleigh quotients, diag(V^H W V))
+    double *sig = nullptr;       // N row norms
+    int *perm = nullptr;         // N: the ascending order
+    unsigned long long *word = nullptr;   // [0] a sweep's worst |c| / sqrt(a b) (bits of a double), [1] its rotations
+};
+
 struct qf_ctx {
     int N = 0;
     int device = 0;
@@ -353,6 +364,7 @@ struct qf_ctx {
     double *slab = nullptr;      // the streamed form's slab: grown on demand to the largest slab planned, never shrunk
     size_t slab_cap = 0;         // bytes ctx->slab has
     qf_sht sht;                  // spherical-harmonic synthesis scratch (sht.hip), grown with the bandwidth
+    qf_eigh_ws eigh;              // Hermitian eigensolver work set (eigh.hip), on demand
 
     double *rowpart = nullptr;   // [tiles_n][N] partial row sums from the GEMM2 epilogue
     int rowpart_tiles = 0;
@@ -551,6 +563,15 @@ void qf_sht_sizes(int L, int isreal, size_t bytes[6]);   // what each ctx->sht b
 int qf_launch_sht_analysis(qf_ctx *ctx, int L, int shr, int isreal, double *omega_dev);
 int qf_launch_sht_qbuild(qf_ctx *ctx, int L);
 void qf_sht_analysis_sizes(int L, int isreal, size_t bytes[8]);   // as qf_sht_sizes; [6] = H, [7] = Q
+
+// ---- eigh.hip: one-sided Jacobi on the rows of G (device pointers)
+// one round of the tournament: every disjoint pair of rows is made orthogonal unless |c| <= tol sqrt(a b)
+int qf_launch_eigh_round(qf_ctx *ctx, cplx *G, int round, double tol, unsigned long long *word);
+int qf_launch_eigh_normalise(qf_ctx *ctx, cplx *G, double *sig);                       // sig[j] = |row j|, row j /= sig[j]
+int qf_launch_eigh_rowdot(qf_ctx *ctx, const cplx *T, const cplx *U, cplx *out);      // out[j] = sum_k T[j,k] conj(U[j,k])
+// out[k,j] = conj(U[perm ? perm[j] : j, k]) * (scale ? scale[j] : 1)
+int qf_launch_eigh_conj_transpose(qf_ctx *ctx, const cplx *U, const int *perm, const cplx *scale, cplx *out);
+int qf_launch_eigh_neg_i(qf_ctx *ctx, const cplx *X, cplx *out);                       // out = -i X; X == nullptr: out = I
 
 // ---- ozaki.hip: complex products on the int8 matrix cores from digit-sliced operands
 struct qf_oz_job {

@@ -1006,6 +1006,23 @@ class DeviceTrajectory:
         _lib.check(self._lib.qf_shr2fun(self.ctx.handle, None, ctypes.c_longlong(n), L, int(bool(berezin)), ptr(f)))
         return f
 
+    def spectrum(self):
+        """The ascending eigenvalues of -i W for the resident state: the invariant of the isospectral flow, by the
+        device eigensolver (qf_eigh_state, quflow_amd.linalg).  Only the N eigenvalues cross PCIe."""
+        self._double_only("spectrum")
+        lam = np.empty(self.N, dtype=np.float64)
+        _lib.check_eigh(self._lib.qf_eigh_state(self.ctx.handle, ptr(lam), None))
+        return lam
+
+    def scale_decomposition(self):
+        """Host (Ws, Wr) of the resident state with P = solve_poisson(W): quflow_amd.analysis.scale_decomposition of
+        `download()`, without the download."""
+        self._double_only("scale_decomposition")
+        Ws = np.empty((self.N, self.N), dtype=np.complex128)
+        Wr = np.empty((self.N, self.N), dtype=np.complex128)
+        _lib.check_eigh(self._lib.qf_scale_decomposition(self.ctx.handle, None, None, ptr(Ws), ptr(Wr)))
+        return Ws, Wr
+
     def download(self):
         W = np.zeros((self.N, self.N), dtype=self.dtype)
         _lib.check((self._lib.qf_c64_download_W if self.c64 else self._lib.qf_download_W)(self.ctx.handle, ptr(W)))
