@@ -328,6 +328,34 @@ int qf_eigh_state(qf_ctx *ctx, double *lambda_host, qf_eigh_stats *stats);
  * (skew-Hermitian form).  Ws_host, Wr_host: (N,N) complex128 each. */
 int qf_scale_decomposition(qf_ctx *ctx, const void *W_host, const void *P_host, void *Ws_host, void *Wr_host);
 
+/* ---- Rotations and gradients on the sphere (csrc/geometry.hip; quflow/geometry.py:132-207).  With s = (N-1)/2 and
+ *      c_a = sqrt((a+1)(N-1-a)) the generators of so(3) in u(N) are S3 = i diag(a - s), S1[a,a+1] = S1[a+1,a] = i c_a / 2,
+ *      S2[a,a+1] = c_a / 2 = -S2[a+1,a]; no kernel stores them.  R = exp(xi . S) by scaling and squaring: with
+ *      b0 = |xi . S|_inf (from the closed forms), sigma = max(0, ceil(log2(b0 / 0.5))) and b = b0 / 2^sigma <= 0.5, the
+ *      degree-d Taylor polynomial of exp(xi . S / 2^sigma), d the smallest degree with b^d / d! < 1e-18, is written by one
+ *      banded kernel and squared sigma times with the ordinary product.  Rounding grows like 2^sigma ~ N |xi|: the
+ *      entrywise error of R is a few N max(1, |xi|) eps.  |xi| is NOT reduced modulo 2 pi (for even N a full turn is
+ *      -I).  complex128 only.  The work set (two N^2 matrices, 3 N^2 for the gradient) is allocated on the context's
+ *      first such call and freed with it. -------- */
+/* Host only, no context: the squarings sigma and the degree d the rule above gives for (N, xi); either may be NULL.
+ * xi = 0: sigma = 0, d = 1.  A non-finite xi (or one that needs more than 64 squarings), N outside 2..8192: QF_ERR_INVALID. */
+int qf_so3_exp_plan(int N, const double xi[3], int *squarings, int *degree);
+/* R_host: (N,N) complex128 = exp(xi[0] S1 + xi[1] S2 + xi[2] S3); NULL leaves the matrix on the device (timing).
+ * A non-finite xi: QF_ERR_INVALID before any launch. */
+int qf_so3_exp(qf_ctx *ctx, const double xi[3], void *R_host);
+/* HIP-event times of the most recent exponential of this context (qf_so3_exp, or the one inside qf_rotate): the Taylor
+ * launch and the sigma squarings, in milliseconds.  QF_ERR_STATE before the first one. */
+int qf_so3_exp_times(qf_ctx *ctx, double *taylor_ms, double *squarings_ms);
+/* out = R W R^H (quflow/geometry.py:154-170) for ANY complex W, R = exp(xi . S).  W_host == NULL: the context's resident
+ * state, rotated in place (out_host may then be NULL; otherwise it receives the new state as well); the context is left
+ * as qf_upload_W leaves it -- the increment of an earlier stepper call is dropped.  An inf or NaN in W:
+ * QF_ERR_NONFINITE, nothing is changed. */
+int qf_rotate(qf_ctx *ctx, const double xi[3], const void *W_host, void *out_host);
+/* dP_host: (3,N,N) complex128, dP[k] = [S_{k+1}, P] -- the reference's grad(P) = bracket(X_k, P) (geometry.py:197-207,
+ * X_k = hbar S_k) up to rounding, in one memory-bound pass instead of six dense products.  P_host == NULL: the
+ * resident state.  dP_host == NULL: the result stays on the device (timing).  An inf or NaN in P: QF_ERR_NONFINITE. */
+int qf_grad(qf_ctx *ctx, const void *P_host, void *dP_host);
+
 /* ---- measurement support (bench.py): HIP-event timing on the ctx stream -------- */
 #define QF_KERNEL_POISSON 0
 #define QF_KERNEL_GEMM1 1

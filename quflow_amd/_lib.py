@@ -140,6 +140,11 @@ SIGNATURES = {
     "qf_eigh_skew": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(EighStats)]),
     "qf_eigh_state": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(EighStats)]),
     "qf_scale_decomposition": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "qf_so3_exp_plan": (ctypes.c_int, [ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "qf_so3_exp": (ctypes.c_int, [_vp, _dp, _vp]),
+    "qf_so3_exp_times": (ctypes.c_int, [_vp, _dp, _dp]),
+    "qf_rotate": (ctypes.c_int, [_vp, _dp, _vp, _vp]),
+    "qf_grad": (ctypes.c_int, [_vp, _vp, _vp]),
     "qf_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "qf_profile_reset": (ctypes.c_int, [_vp]),
     "qf_profile_read": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), _dp]),
@@ -204,8 +209,9 @@ def check(rc):
 
 
 def check_eigh(rc):
-    """`check` for the eigensolver's entry points: there QF_ERR_NONFINITE is an inf / NaN entry of the INPUT, not a stepper's
-    residual, and is reported as the library's own error with its message."""
+    """`check` for the eigensolver's entry points (and the rotations and gradients of quflow_amd.geometry): there
+    QF_ERR_NONFINITE is an inf / NaN entry of the INPUT, not a stepper's residual, and is reported as the library's own error
+    with its message."""
     if rc != QF_OK:
         msg = load().qf_last_error()
         raise QuflowHipError("%s: %s" % (ERR_NAMES.get(rc, "error %d" % rc),

@@ -227,6 +227,11 @@ int qf_ctx_destroy(qf_ctx *ctx)
     void *eigh[] = {ctx->eigh.H, ctx->eigh.G, ctx->eigh.V, ctx->eigh.ray, ctx->eigh.sig, ctx->eigh.perm, ctx->eigh.word};
     for (void *p : eigh)
         if (p) (void)hipFree(p);
+    void *geom[] = {ctx->geom.R[0], ctx->geom.R[1], ctx->geom.grad};
+    for (void *p : geom)
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : ctx->geom.ev)
+        if (e) (void)hipEventDestroy(e);
     for (cplx *p : ctx->multi)
         if (p) (void)hipFree(p);
     for (int q = 0; q < 4; ++q) {

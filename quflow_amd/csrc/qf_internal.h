@@ -293,6 +293,14 @@ struct qf_eigh_ws {
     unsigned long long *word = nullptr;   // [0] a sweep's worst |c| / sqrt(a b) (bits of a double), [1] its rotations
 };
 
+// Work set of the rotations and gradients (geometry.hip, api_geometry.hip): allocated on first use, freed with the context.
+struct qf_geom_ws {
+    cplx *R[2] = {nullptr, nullptr};     // the Taylor start and its squarings, alternating; then R and R^H
+    cplx *grad = nullptr;                // (3, N, N): the three commutators [S_k, P]
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // around the Taylor launch and the squarings of the last exponential
+    bool timed = false;                  // ev[] were recorded by a completed qf_so3_exp / qf_rotate
+};
+
 struct qf_ctx {
     int N = 0;
     int device = 0;
@@ -365,6 +373,7 @@ struct qf_ctx {
     size_t slab_cap = 0;         // bytes ctx->slab has
     qf_sht sht;                  // spherical-harmonic synthesis scratch (sht.hip), grown with the bandwidth
     qf_eigh_ws eigh;              // Hermitian eigensolver work set (eigh.hip), on demand
+    qf_geom_ws geom;              // rotation / gradient work set (geometry.hip), on demand
 
     double *rowpart = nullptr;   // [tiles_n][N] partial row sums from the GEMM2 epilogue
     int rowpart_tiles = 0;
@@ -572,6 +581,14 @@ int qf_launch_eigh_rowdot(qf_ctx *ctx, const cplx *T, const cplx *U, cplx *out);
 // out[k,j] = conj(U[perm ? perm[j] : j, k]) * (scale ? scale[j] : 1)
 int qf_launch_eigh_conj_transpose(qf_ctx *ctx, const cplx *U, const int *perm, const cplx *scale, cplx *out);
 int qf_launch_eigh_neg_i(qf_ctx *ctx, const cplx *X, cplx *out);                       // out = -i X; X == nullptr: out = I
+
+// ---- geometry.hip: exp(xi . S) and the gradient from the closed-form so(3) generators (device pointers)
+#define QF_SO3_STRIP 32             // columns a workgroup of k_so3_taylor owns
+#define QF_SO3_MAX_DEGREE 16        // the largest Taylor degree the scaling rule asks for (b <= 0.5)
+// the scaling rule, host only: squarings sigma, Taylor degree d, and b = |xi . S|_inf / 2^sigma <= 0.5 (any may be NULL)
+int qf_so3_plan(int N, const double xi[3], int *squarings, int *degree, double *b_scaled);
+int qf_launch_so3_taylor(qf_ctx *ctx, const double xi[3], int squarings, int degree, cplx *T);   // T = p_d(xi . S / 2^sigma)
+int qf_launch_so3_grad(qf_ctx *ctx, const cplx *P, cplx *out);                                  // out[k] = [S_k, P], (3,N,N)
 
 // ---- ozaki.hip: complex products on the int8 matrix cores from digit-sliced operands
 struct qf_oz_job {

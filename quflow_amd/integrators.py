@@ -1023,6 +1023,23 @@ class DeviceTrajectory:
         _lib.check_eigh(self._lib.qf_scale_decomposition(self.ctx.handle, None, None, ptr(Ws), ptr(Wr)))
         return Ws, Wr
 
+    def rotate(self, xi):
+        """Rotate the resident state in place, W <- R W R^H with R = exp(xi . S) (quflow_amd.geometry.rotate of
+        `download()`, bit for bit, without any transfer).  The next `advance` starts as after an `upload`.  Returns self."""
+        self._double_only("rotate")
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        if xi.shape != (3,):
+            raise ValueError("xi must have shape (3,), got %s" % (xi.shape,))
+        _lib.check_eigh(self._lib.qf_rotate(self.ctx.handle, xi.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), None, None))
+        return self
+
+    def grad(self):
+        """(3,N,N) host array: quflow_amd.geometry.grad of the resident state, without the upload."""
+        self._double_only("grad")
+        dP = np.empty((3, self.N, self.N), dtype=np.complex128)
+        _lib.check_eigh(self._lib.qf_grad(self.ctx.handle, None, ptr(dP)))
+        return dP
+
     def download(self):
         W = np.zeros((self.N, self.N), dtype=self.dtype)
         _lib.check((self._lib.qf_c64_download_W if self.c64 else self._lib.qf_download_W)(self.ctx.handle, ptr(W)))

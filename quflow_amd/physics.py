@@ -53,3 +53,24 @@ def inner_H1(P1, P2):
 def norm_H1(P):
     """quflow/physics.py:20-21."""
     return np.sqrt(inner_H1(P, P))
+
+
+def sectional_curvature(F, G):
+    """The sectional curvature expression of quflow/physics.py:41-58 for the pair (F, G), composed of the device
+    `laplace`, `solve_poisson`, `commutator` and the host `inner_L2` exactly as there."""
+    from . import integrators
+    from .geometry import inner_L2
+    from .laplacian import laplace, solve_poisson
+    commutator = integrators.commutator
+    LF, LG = laplace(F), laplace(G)
+    FG = commutator(F, G)
+    LF_G = commutator(LF, G)
+    LG_F = commutator(LG, F)
+    LF_F = commutator(LF, F)
+    LG_G = commutator(LG, G)
+    sym = LF_G + LG_F
+    C = -inner_L2(sym, solve_poisson(sym)) / 4.0
+    C -= inner_L2(FG, LF_G - LG_F) / 2.0
+    C += inner_L2(FG, laplace(FG)) * (3.0 / 4.0)
+    C += inner_L2(LF_F, solve_poisson(LG_G))
+    return C

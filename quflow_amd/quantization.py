@@ -1,7 +1,7 @@
 """Spherical-harmonics <-> matrix transforms of quflow on the MI355X.
 
 Mirrors `quflow.quantization` (quflow/quantization.py): `shr2mat`, `mat2shr`, `shc2mat`,
-`mat2shc`, `get_basis`, `compute_basis`, `basis_break_index` with the reference's names,
+`mat2shc`, `get_basis`, `compute_basis`, `basis_break_index`, `elmr2mat`, `elmc2mat` with the reference's names,
 argument meaning and conventions, so that initial data (`shr2mat(omega, N)`) and every
 'shr' output of a run (`mat2shr(W)`, quflow/simulation.py:287-344) come from the device.
 
@@ -119,6 +119,55 @@ def get_basis(N, allow_compute=True, dtype=np.double):
     if basis is not None:
         _basis_cache[key] = basis
     return basis
+
+
+def _basis_column(el, absm, N):
+    """Column el - |m| of the |m| block of the basis: the |m|-th diagonal of T_{el,|m|}, N - |m| real numbers."""
+    if not 0 <= absm <= el < N:
+        raise ValueError("need 0 <= |m| <= el < N, got el=%d, m=%d, N=%d" % (el, absm, N))
+    basis = get_basis(N)
+    n = N - absm
+    block = basis[basis_break_index(absm, N):basis_break_index(absm + 1, N)].reshape((n, n))
+    return block[:, el - absm]
+
+
+def elmr2mat(el, m, N, dtype=np.cdouble):
+    """The real basis element T_{el,m} of u(N) as a scipy `dia_matrix` with the attribute `.el`
+    (quflow/quantization.py:586-634), unit norm_L2.  The basis comes from the device (`get_basis`)."""
+    from scipy.sparse import dia_matrix
+    absm = abs(int(m))
+    cdtype = np.complex64 if np.dtype(dtype) in (np.dtype(np.complex64), np.dtype(np.float32)) else np.complex128
+    col = _basis_column(int(el), absm, N).astype(cdtype)
+    if m == 0:
+        T = dia_matrix((1.0j * col, 0), shape=(N, N))
+    else:
+        sgn = -1.0 if absm % 2 else 1.0
+        d = col * ((sgn if m < 0 else 1.0j * sgn) / np.sqrt(2))
+        data = np.zeros((2, N), dtype=cdtype)
+        data[0, :N - absm] = -d.conj()
+        data[1, absm:] = d
+        T = dia_matrix((data, np.array([-absm, absm])), shape=(N, N))
+    T.el = el
+    return T
+
+
+def elmc2mat(el, m, N, dtype=np.cdouble):
+    """The complex basis element T_{el,m} of gl(N, C) as a scipy `dia_matrix` with the attribute `.el`
+    (quflow/quantization.py:637-678), unit norm_L2."""
+    from scipy.sparse import dia_matrix
+    m = int(m)
+    absm = abs(m)
+    cdtype = np.complex64 if np.dtype(dtype) in (np.dtype(np.complex64), np.dtype(np.float32)) else np.complex128
+    col = _basis_column(int(el), absm, N)
+    data = np.zeros(N, dtype=cdtype)
+    if m >= 0:
+        data[:N - absm] = col
+    else:
+        data[absm:] = col
+    data *= 1.0j if (m >= 0 or m % 2 == 0) else -1.0j
+    T = dia_matrix((data, -m), shape=(N, N))
+    T.el = el
+    return T
 
 
 def set_basis(N, basis):
