@@ -274,8 +274,8 @@ def conj_subtract_(a):
 def isomp_fixedpoint(W, dt, steps=100, hamiltonian=solve_poisson, time=None, forcing=None,
                      strang_splitting=None, stats=None, callback=None, tol='auto', maxit=10,
                      minit=1, verbatim=False, compsum=False, reinitialize=False):
-    """quflow/integrators/isospectral.py:338-613, statement by statement
-    (skew-Hermitian branch; forcing / strang_splitting hooks included)."""
+    """quflow/integrators/isospectral.py:338-613, statement by statement (forcing / strang_splitting hooks
+    included; select_skewherm(False) takes the general commutator of :504-505 as well as the general solve)."""
     assert minit >= 1, "minit must be at least 1."
     assert maxit >= minit, "maxit must be at minit."
 
@@ -348,7 +348,10 @@ def isomp_fixedpoint(W, dt, steps=100, hamiltonian=solve_poisson, time=None, for
             Phalf *= vareps                                        # :492
             np.matmul(Phalf, Whalf, out=PWcomm)                    # :496
             np.matmul(PWcomm, Phalf, out=dW)                       # :499
-            conj_subtract_(PWcomm)                                 # :503
+            if _SKEWH:                                             # :500
+                conj_subtract_(PWcomm)                             # :503
+            else:
+                PWcomm -= Whalf @ Phalf                            # :505
             dW += PWcomm                                           # :509
             if forcing:                                            # :512-520
                 Phalf /= vareps

@@ -543,10 +543,16 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
                     } else {
                         QF_TRY_R(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + 1));
                     }
-                } else if (j < 48 && i + 1 >= minit) {
+                } else if (i + 1 >= minit) {
                     // the exit test looks at state 0's residual, but scipy.linalg.norm checks the WHOLE stack for infs / NaNs
-                    // before it reduces (check_finite, isospectral.py:528): the other states' norms are formed for that check
-                    QF_TRY_R(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + 16 + j));
+                    // before it reduces (check_finite, isospectral.py:528): the other states' norms are formed for that check --
+                    // 48 result slots, the states beyond them folded on the device into scalars[8] (through scalars[9])
+                    QF_TRY_R(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + (j < 48 ? 16 + j : 9)));
+                    if (j == 48 && hipMemsetAsync(ctx->scalars + 8, 0, sizeof(double), ctx->stream) != hipSuccess) {
+                        qf_set_error("qf_isomp_states: clearing the folded finite flag failed");
+                        return restore(QF_ERR_HIP);
+                    }
+                    if (j >= 48) QF_TRY_R(qf_launch_fold_nonfinite(ctx, ctx->scalars + 9, ctx->scalars + 8));
                 }
                 S[j].cur ^= 1;
             }
@@ -558,8 +564,12 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
                     qf_set_error("qf_isomp_states: copy of the states' residual norms failed");
                     return restore(QF_ERR_HIP);
                 }
+                if (k > 48 && hipMemcpyAsync(ctx->host_scalars + 48, ctx->scalars + 8, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+                    qf_set_error("qf_isomp_states: copy of the folded finite flag failed");
+                    return restore(QF_ERR_HIP);
+                }
                 QF_TRY_R(read_scalar(ctx, ctx->scalars + 1, &resnorm));
-                bool finite = QF_FINITE(resnorm);
+                bool finite = QF_FINITE(resnorm) && (k <= 48 || QF_FINITE(ctx->host_scalars[48]));
                 for (int j = 1; j < kk; ++j) finite = finite && QF_FINITE(ctx->host_scalars[j]);
                 if (!finite) {       // scipy.linalg.norm raises here (isospectral.py:534, mhd.py: same test)
                     qf_set_error("array must not contain infs or NaNs");

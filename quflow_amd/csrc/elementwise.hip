@@ -407,6 +407,14 @@ __global__ __launch_bounds__(1024) void k_max_rows(int N, int tiles, const doubl
     }
 }
 
+// acc = NaN once `in` is an inf or a NaN (one thread): the finite check of the states of a stack beyond the 48 result
+// slots, folded into one scalar on the device (the host zeroes acc before the first fold of an exit test)
+__global__ void k_fold_nonfinite(const double *__restrict__ in, double *__restrict__ acc)
+{
+    const double v = in[0];
+    if (!QF_FINITE(v)) acc[0] = __builtin_nan("");
+}
+
 // max |A[i,j] + conj(A[j,i])| and max |A[i,j]| over the rows of one block (NaN-propagating:
 // a NaN anywhere makes the defect NaN, which fails the host's `<=` test).
 // (the sums in C's real type, as A + A^H of the reference's arrays)
@@ -792,6 +800,13 @@ int qf_launch_state_init(qf_ctx *ctx, double tol, int minit, int maxit, const do
 int qf_launch_norm_from_rowpart(qf_ctx *ctx, const double *rowpart, int tiles, double *out_dev)
 {
     hipLaunchKernelGGL(k_max_rows, dim3(1), dim3(1024), 0, ctx->stream, ctx->N, tiles, rowpart, out_dev);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+int qf_launch_fold_nonfinite(qf_ctx *ctx, const double *in_dev, double *acc_dev)
+{
+    hipLaunchKernelGGL(k_fold_nonfinite, dim3(1), dim3(1), 0, ctx->stream, in_dev, acc_dev);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }

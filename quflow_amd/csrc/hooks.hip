@@ -456,13 +456,19 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
             // (`resnormvec.max()`, :527-532); with a shared one it looks at state 0's, but scipy.linalg.norm checks the WHOLE
             // stack for infs / NaNs before it reduces (check_finite, :528) -- a NaN in a passively advected state raises
             // there, so it is an error return here too.  (magmp: state 0's row sums are completed by the magnetic terms
-            // below; the finite check of its second state is the one of qf_isomp_states.)
-            const bool norms_all = (per_state || !magnetic) && k <= 48;
+            // below; the finite check of its second state is the one of qf_isomp_states.)  The result slots scalars[16..63]
+            // take 48 norms; the states beyond them (shared stream matrix only) are wanted for the finite check alone and are
+            // folded on the device into scalars[8] (through scalars[9]).
+            const bool norms_all = per_state || !magnetic;
+            if (norms_all && k > 48 && i + 1 >= minit) QF_HIP(hipMemsetAsync(ctx->scalars + 8, 0, sizeof(double), ctx->stream));
             for (int j = 0; j < k; ++j) {
                 double *rp = (j == 0 || norms_all) ? ctx->multi_rowpart : (magnetic && j == 1) ? ctx->multi_rowpart + (size_t)slots * N : nullptr;
                 QF_TRY(launch_assemble(ctx, skew, S[j].PW, S[j].dW[S[j].cur ^ 1], (forced && !magnetic) ? S[j].F : nullptr, S[j].W,
                                        S[j].Whalf, S[j].dW[S[j].cur], rp));
-                if (norms_all && i + 1 >= minit) QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + 16 + j));
+                if (norms_all && i + 1 >= minit) {
+                    QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + (j < 48 ? 16 + j : 9)));
+                    if (j >= 48) QF_TRY(qf_launch_fold_nonfinite(ctx, ctx->scalars + 9, ctx->scalars + 8));
+                }
                 // magmp: the second state's residual norm, for the finite check alone (its force term has not joined yet: a
                 // non-finite force shows in the next iteration's Whalf)
                 if (magnetic && j == 1 && i + 1 >= minit) QF_TRY(qf_launch_norm_from_rowpart(ctx, rp, slots, ctx->scalars + 17));
@@ -487,8 +493,13 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
                 if (norms_all) {
                     const int kk = k < 48 ? k : 48;
                     QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 16, (size_t)kk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                    if (k > 48) QF_HIP(hipMemcpyAsync(ctx->host_scalars + 48, ctx->scalars + 8, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
                     QF_HIP(hipStreamSynchronize(ctx->stream));
                     resnorm = ctx->host_scalars[0];
+                    if (k > 48 && !QF_FINITE(ctx->host_scalars[48])) {      // a state beyond the 48 slots: check_finite again
+                        qf_set_error("array must not contain infs or NaNs");
+                        return QF_ERR_NONFINITE;
+                    }
                     for (int j = 1; j < kk; ++j) {
                         const double r = ctx->host_scalars[j];
                         if (per_state) {                 // numpy's max: a NaN wins

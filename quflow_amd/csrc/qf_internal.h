@@ -632,6 +632,8 @@ int qf_launch_update(qf_ctx *ctx, const C *PW, C *W, const C *dW_a, const C *dW_
                      int reinitialize, qf_guard guard = qf_guard());
 int qf_launch_debug_modulus(qf_ctx *ctx, int n, const double *er, const double *ei, double *out_mod, double *out_sqrt);
 int qf_launch_norm_from_rowpart(qf_ctx *ctx, const double *rowpart, int tiles, double *out_dev);
+// *acc_dev = NaN if *in_dev is an inf or a NaN, else unchanged: many norms' finite check folded into one scalar
+int qf_launch_fold_nonfinite(qf_ctx *ctx, const double *in_dev, double *acc_dev);
 // residual norm + exit decision of iteration `guard.iter` (isospectral.py:523-536), on device
 int qf_launch_norm_decide(qf_ctx *ctx, const double *rowpart, int tiles, qf_guard guard);
 // norm_dev != nullptr: automatic tolerance tol = tol_factor * (*norm_dev), formed on the device

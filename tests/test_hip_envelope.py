@@ -402,6 +402,51 @@ def test_nonfinite_entry_in_a_passive_state_of_a_stack_raises(qfa, oracle):
     assert maxabs(Wg, Wc) <= STEP_TOL and sg["iterations"] == sc["iterations"]
 
 
+@pytest.mark.parametrize("k", [48, 49, 64])
+def test_nonfinite_entry_in_the_last_state_of_a_tall_stack_raises(qfa, oracle, k, monkeypatch):
+    """The same check past the 48 result slots the host loops read the states' residual norms from: a NaN in the LAST state of a
+    stack of 48, 49 and 64 (shared stream matrix, so that state never enters the exit decision).  The oracle raises the
+    reference's ValueError; the device call must come back with QF_ERR_NONFINITE (the code is looked at where the Python mirror
+    receives it, and the mirror turns it into the same ValueError) from both host loops: qf_isomp_states (the plain stack) and
+    qf_isomp_hooked (the stack with a forcing).  Before the norms beyond the slots were folded on the device, k > 48 returned
+    QF_OK and a stack with a NaN state."""
+    from quflow_amd import _lib
+    N = 8
+    dt = 0.25 * qfa.hbar(N)
+    S = np.stack([oracle.make_W0(N, j) for j in range(k)])
+    Sb = S.copy()
+    Sb[k - 1, 3, 5] = np.nan
+    Sb[k - 1, 5, 3] = np.nan
+    codes = []
+    plain_check = _lib.check
+
+    def recording_check(rc):
+        codes.append(rc)
+        return plain_check(rc)
+    monkeypatch.setattr(_lib, "check", recording_check)
+    with pytest.raises(ValueError, match="infs or NaNs"):
+        oracle.isomp(Sb.copy(), dt, steps=2)
+    for kw in ({}, {"forcing": lambda P, W: 0.0 * np.nan_to_num(W)}):
+        del codes[:]
+        with pytest.raises(ValueError, match="infs or NaNs"):
+            qfa.isomp(Sb.copy(), dt, steps=2, **kw)
+        assert codes[-1] == _lib.QF_ERR_NONFINITE and _lib.ERR_NAMES[codes[-1]] == "QF_ERR_NONFINITE", codes
+
+
+def test_tall_finite_stack_agrees_with_the_oracle(qfa, oracle):
+    """A finite stack of 49 states at N = 8 (one state past the result slots) through both host loops: the folded finite check
+    changes no state and no iteration count."""
+    N, k = 8, 49
+    dt = 0.25 * qfa.hbar(N)
+    S = np.stack([oracle.make_W0(N, j) for j in range(k)])
+    for kw in ({}, {"forcing": lambda P, W: -0.05 * W + 0.02 * P}):
+        sg, sc = {"iterations": 0.0}, {"iterations": 0.0}
+        Wg = qfa.isomp(S.copy(), dt, steps=3, stats=sg, **kw)
+        Wc = oracle.isomp(S.copy(), dt, steps=3, stats=sc, **kw)
+        assert maxabs(Wg, Wc) <= STEP_TOL and sg["iterations"] == sc["iterations"], (sorted(kw), maxabs(Wg, Wc), sg, sc)
+        assert sc["iterations"] >= 2.0 and sc["number_of_maxit"] == 0.0
+
+
 def test_commutators_combine_on_the_device_to_the_hosts_bits(qfa):
     """qf_commutator (round 6): commutator_skewherm / commutator_generic (isospectral.py:22-57) form X - X^H / W@P - P@W on the
     device -- one PCIe round trip instead of a host pass over N^2 entries -- with the bits of the device product followed by
