@@ -98,6 +98,29 @@ int qf_solve_tridiagonal(qf_ctx *ctx, const double *lap_host, unsigned long long
  * with a different table (fingerprint of 4096 sampled entries) is refactored.  Entries / bytes held: */
 int qf_factor_cache_stats(qf_ctx *ctx, int *entries, unsigned long long *device_bytes);
 
+/* ---- the Hamiltonian of the flow.  Built in: P = Delta^-1 W.  Installed: P = T^-1 (W - F) with T any tridiagonal
+ * (N,N,2) coefficient table (global quasi-geostrophic, Charney-Hasegawa-Mima, Helmholtz-type operators) and F a fixed
+ * N x N complex128 offset (Coriolis term, topography).  Every complex128 stepper of this library that forms the stream
+ * matrix of the flow with the skew-Hermitian solve -- qf_isomp / _continue / _diag / _multi / _states, the native branch
+ * of qf_isomp_hooked, qf_erk / qf_erk_states, qf_isomp_simple / _quasinewton -- follows what is installed on its context,
+ * on the device: the offset is subtracted inside the solve kernel while it loads its right-hand side.
+ *   table_host  (N,N,2) doubles, NULL = the built-in Laplacian.  Factorised into a pair the context owns (never recycled
+ *               by the qf_solve_tridiagonal cache).
+ *   offset_host N x N complex128, NULL = none.  Must be exactly skew-Hermitian: the solve reads its upper triangle only
+ *               (the caller checks; quflow_amd.TridiagonalHamiltonian does).
+ *   *_key       caller-chosen ids (0: always refactor / upload again).  A call that repeats the key AND the fingerprint
+ *               (4096 sampled entries, as qf_solve_tridiagonal) of what the context still holds neither refactors nor uploads.
+ * Not followed (they keep the built-in solve): the complex64 entry points, the general (skewh = 0) branches, magmp,
+ * qf_solve_poisson, qf_diagnostics / qf_isomp_diag (energy_euler stays the Euler energy -<W, Delta^-1 W>/2),
+ * qf_scale_decomposition. */
+int qf_set_hamiltonian(qf_ctx *ctx, const double *table_host, unsigned long long table_key, const void *offset_host,
+                       unsigned long long offset_key);
+int qf_clear_hamiltonian(qf_ctx *ctx);      /* back to the built-in Poisson Hamiltonian (the buffers are kept) */
+/* P = T^-1 (W - F) with what is installed; host in, host out */
+int qf_hamiltonian(qf_ctx *ctx, const void *W_host, void *P_host);
+/* H = -inner_L2(P, W - F)/2 of the resident state, P = T^-1 (W - F): the conserved energy when T is symmetric */
+int qf_hamiltonian_energy(qf_ctx *ctx, double *H);
+
 /* ---- stepper protocol: isomp_fixedpoint (quflow/integrators/isospectral.py:338-613),
  *      called by simulation.solve (quflow/simulation.py:788) ---------------------- */
 int qf_upload_W(qf_ctx *ctx, const void *W_host);     /* host -> ctx state W */

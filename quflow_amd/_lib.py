@@ -84,6 +84,10 @@ SIGNATURES = {
     "qf_solve_poisson": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int]),
     "qf_laplace": (ctypes.c_int, [_vp, _vp, _vp]),
     "qf_solve_tridiagonal": (ctypes.c_int, [_vp, _vp, ctypes.c_ulonglong, _vp, _vp, ctypes.c_int]),
+    "qf_set_hamiltonian": (ctypes.c_int, [_vp, _vp, ctypes.c_ulonglong, _vp, ctypes.c_ulonglong]),
+    "qf_clear_hamiltonian": (ctypes.c_int, [_vp]),
+    "qf_hamiltonian": (ctypes.c_int, [_vp, _vp, _vp]),
+    "qf_hamiltonian_energy": (ctypes.c_int, [_vp, _dp]),
     "qf_factor_cache_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ulonglong)]),
     "qf_comm_unique_id": (ctypes.c_int, [_vp]),
     "qf_comm_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),

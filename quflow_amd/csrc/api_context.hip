@@ -72,6 +72,15 @@ int qf_plan_describe(qf_ctx *ctx, char *buf, int n)
         out += "\": ";
         out += ctx->plan[r].text[0] ? ctx->plan[r].text : "null";
     }
+    // the Hamiltonian of the flow (qf_set_hamiltonian): what the stream matrix is formed with
+    if (ctx->ham_table || ctx->ham_offset_on) {
+        char h[160];
+        if (ctx->ham_table) snprintf(h, sizeof(h), ", \"hamiltonian\": {\"table_key\": %llu, \"offset\": %s}", ctx->ham_key, ctx->ham_offset_on ? "true" : "false");
+        else snprintf(h, sizeof(h), ", \"hamiltonian\": {\"table_key\": null, \"offset\": true}");
+        out += h;
+    } else {
+        out += ", \"hamiltonian\": \"poisson\"";
+    }
     out += "}";
     if (n > 0) {
         const size_t m = out.size() < (size_t)(n - 1) ? out.size() : (size_t)(n - 1);
@@ -217,7 +226,7 @@ int qf_ctx_destroy(qf_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     void *ptrs[] = {ctx->W, ctx->dW[0], ctx->dW[1], ctx->Whalf, ctx->Phalf, ctx->PW, ctx->kahan_c, ctx->stage,
-                    ctx->lap, ctx->lap_user, ctx->poisson.tab, ctx->rowpart, ctx->rowsum,
+                    ctx->lap, ctx->lap_user, ctx->poisson.tab, ctx->ham.tab, ctx->ham_offset, ctx->rowpart, ctx->rowsum,
                     ctx->t32_partial, ctx->t32_arrive, ctx->W2, ctx->Whalf2, ctx->ns_inv, ctx->ns_tmp, ctx->multi_rowpart, ctx->scalars, ctx->sk_partial, ctx->sk_flags, ctx->basis, ctx->sh_stage, ctx->sh_omega, ctx->slab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);

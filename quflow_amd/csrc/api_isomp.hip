@@ -55,7 +55,7 @@ template <class S> double mach_eps(bool root)
 // the two launchers that differ between the precisions (the table source, the kernel family), overloaded on the element type
 int launch_solve(qf_ctx *ctx, const cplx *W, cplx *P, double vareps, qf_guard g, const qf_decide *dec = nullptr)
 {
-    return qf_launch_solve(ctx, ctx->poisson, W, P, vareps, 1, g, dec);
+    return qf_launch_hamiltonian(ctx, W, P, vareps, g, dec);
 }
 // (the scale is applied in float32, as `Phalf *= vareps` on a complex64 array is: isospectral.py:488-492)
 int launch_solve(qf_ctx *ctx, const float2 *W, float2 *P, double vareps, qf_guard g)
@@ -294,7 +294,7 @@ int enqueue_iterations_fused_i8(qf_ctx *ctx, int step, int first, int count, dou
         g.alt = ctx->Whalf2;
         {
             prof_scope p(ctx, QF_KERNEL_POISSON);
-            QF_TRY(qf_launch_solve(ctx, ctx->poisson, ctx->Whalf, ctx->Phalf, vareps, 1, g));
+            QF_TRY(qf_launch_hamiltonian(ctx, ctx->Whalf, ctx->Phalf, vareps, g));
         }
         if (ctx->gemm_i8_hybrid) {
             // hybrid: PW = Phalf @ Whalf in fp64 (k_zgemm), then PW and Phalf are sliced in one launch for the

@@ -11,6 +11,25 @@
 
 #include "qf_api.h"
 
+namespace {
+// fingerprint of a caller's array of n doubles: 4096 entries spread over it and the last one (FNV-1a over their bit
+// patterns).  A key is a caller-side hash; the fingerprint catches a key that returns with different content.
+unsigned long long sample_fingerprint(const double *a, size_t n)
+{
+    unsigned long long fp = 1469598103934665603ull;
+    const size_t stride = n / 4096 ? n / 4096 : 1;
+    for (size_t i = 0; i < n; i += stride) {
+        unsigned long long bits;
+        memcpy(&bits, a + i, sizeof(bits));
+        fp = (fp ^ bits) * 1099511628211ull;
+    }
+    unsigned long long bits;
+    memcpy(&bits, a + (n - 1), sizeof(bits));
+    fp = (fp ^ bits) * 1099511628211ull;
+    return fp;
+}
+}  // namespace
+
 extern "C" {
 
 int qf_laplacian_table(qf_ctx *ctx, int bc, double *lap_host)
@@ -72,20 +91,7 @@ int qf_solve_tridiagonal(qf_ctx *ctx, const double *lap_host, unsigned long long
         return QF_ERR_INVALID;
     }
     const size_t NN = (size_t)ctx->N * ctx->N;
-    // fingerprint of the caller's table: 4096 entries spread over it (FNV-1a over their bit patterns).
-    // A key is a caller-side hash; the fingerprint catches a key that returns with different content.
-    unsigned long long fp = 1469598103934665603ull;
-    {
-        const size_t n = 2 * NN, stride = n / 4096 ? n / 4096 : 1;
-        for (size_t i = 0; i < n; i += stride) {
-            unsigned long long bits;
-            memcpy(&bits, lap_host + i, sizeof(bits));
-            fp = (fp ^ bits) * 1099511628211ull;
-        }
-        unsigned long long bits;
-        memcpy(&bits, lap_host + (n - 1), sizeof(bits));
-        fp = (fp ^ bits) * 1099511628211ull;
-    }
+    const unsigned long long fp = sample_fingerprint(lap_host, 2 * NN);
     qf_factors f;
     auto it = ctx->user_factors.find(table_key);
     const bool hit = table_key != 0 && it != ctx->user_factors.end() && it->second.fingerprint == fp;
@@ -129,6 +135,87 @@ int qf_solve_tridiagonal(qf_ctx *ctx, const double *lap_host, unsigned long long
     QF_TRY(qf_launch_solve(ctx, f, ctx->stage, ctx->Phalf, 1.0, skewh));
     QF_HIP(hipMemcpyAsync(P_host, ctx->Phalf, NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
+// ---- the installed Hamiltonian of the flow (include/quflow_hip.h; launched through qf_launch_hamiltonian, poisson.hip)
+int qf_set_hamiltonian(qf_ctx *ctx, const double *table_host, unsigned long long table_key, const void *offset_host,
+                       unsigned long long offset_key)
+{
+    QF_TRY(check_ctx(ctx));
+    const size_t NN = (size_t)ctx->N * ctx->N;
+    // nothing is in force until both parts are in place: an error below leaves the built-in Hamiltonian
+    ctx->ham_table = false;
+    ctx->ham_offset_on = false;
+    if (table_host) {
+        const unsigned long long fp = sample_fingerprint(table_host, 2 * NN);
+        if (!(ctx->ham.tab && table_key != 0 && ctx->ham_key == table_key && ctx->ham_fp == fp)) {
+            if (!ctx->ham.tab) QF_TRY(alloc_factors(ctx, &ctx->ham));
+            if (!ctx->lap_user) QF_HIP(hipMalloc((void **)&ctx->lap_user, 2 * NN * sizeof(double)));
+            ctx->ham_key = 0;      // (what the pair holds is undefined until the factorisation has been queued)
+            // (pageable source: hipMemcpyAsync returns after staging, the caller's table is free on return)
+            QF_HIP(hipMemcpyAsync(ctx->lap_user, table_host, 2 * NN * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            QF_TRY(qf_launch_build_factors(ctx, ctx->lap_user, ctx->ham));
+            ctx->ham_key = table_key;
+            ctx->ham_fp = fp;
+        }
+    }
+    if (offset_host) {
+        const unsigned long long fp = sample_fingerprint(static_cast<const double *>(offset_host), 2 * NN);
+        if (!(ctx->ham_offset && offset_key != 0 && ctx->ham_offset_key == offset_key && ctx->ham_offset_fp == fp)) {
+            if (!ctx->ham_offset) QF_HIP(hipMalloc((void **)&ctx->ham_offset, NN * sizeof(cplx)));
+            ctx->ham_offset_key = 0;
+            QF_HIP(hipMemcpyAsync(ctx->ham_offset, offset_host, NN * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+            ctx->ham_offset_key = offset_key;
+            ctx->ham_offset_fp = fp;
+        }
+    }
+    ctx->ham_table = table_host != nullptr;
+    ctx->ham_offset_on = offset_host != nullptr;
+    return QF_OK;
+}
+
+int qf_clear_hamiltonian(qf_ctx *ctx)
+{
+    QF_TRY(check_ctx(ctx));
+    ctx->ham_table = false;
+    ctx->ham_offset_on = false;
+    return QF_OK;
+}
+
+int qf_hamiltonian(qf_ctx *ctx, const void *W_host, void *P_host)
+{
+    QF_TRY(check_ctx(ctx));
+    if (!W_host || !P_host) {
+        qf_set_error("qf_hamiltonian: null buffer");
+        return QF_ERR_INVALID;
+    }
+    const size_t bytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    QF_HIP(hipMemcpyAsync(ctx->stage, W_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    QF_TRY(qf_launch_hamiltonian(ctx, ctx->stage, ctx->Phalf, 1.0));
+    QF_HIP(hipMemcpyAsync(P_host, ctx->Phalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
+int qf_hamiltonian_energy(qf_ctx *ctx, double *H)
+{
+    QF_TRY(check_ctx(ctx));
+    if (!H) {
+        qf_set_error("qf_hamiltonian_energy: null output");
+        return QF_ERR_INVALID;
+    }
+    // D = W - F once (stage), P = T^-1 D (Phalf), then <P, D>: the sum the definition names, no difference of two sums
+    const cplx *D = ctx->W;
+    if (ctx->ham_offset_on) {
+        QF_TRY(qf_launch_lincomb(ctx, 1.0, ctx->W, -1.0, ctx->ham_offset, 0.0, ctx->stage));
+        D = ctx->stage;
+    }
+    QF_TRY(qf_launch_solve(ctx, ctx->ham_table ? ctx->ham : ctx->poisson, D, ctx->Phalf, 1.0, 1));
+    QF_TRY(qf_launch_inner(ctx, ctx->Phalf, D, ctx->scalars + 2));
+    double pd = 0.0;
+    QF_TRY(read_scalar(ctx, ctx->scalars + 2, &pd));
+    *H = -(pd / ctx->N) / 2.0;
     return QF_OK;
 }
 

@@ -39,7 +39,8 @@ int qf_erk(qf_ctx *ctx, int method, double dt, int steps, int skewh)
     auto products = [&](const cplx *X) -> int {
         {
             prof_scope p(ctx, QF_KERNEL_POISSON);
-            QF_TRY(qf_launch_solve(ctx, ctx->poisson, X, P, 1.0, skewh ? 1 : 0));
+            if (skewh) QF_TRY(qf_launch_hamiltonian(ctx, X, P, 1.0));
+            else QF_TRY(qf_launch_solve(ctx, ctx->poisson, X, P, 1.0, 0));
         }
         {
             prof_scope p(ctx, QF_KERNEL_GEMM1);
@@ -117,7 +118,8 @@ int qf_erk_states(qf_ctx *ctx, void *states_host, int k, int method, double dt, 
     cplx *P = ctx->Phalf, *A = ctx->PW, *B = ctx->stage;
     // one stage for the whole stack: P from the stage argument of state 0, then every state's slope
     auto stage_all = [&](bool from_state, double c_acc, bool want_wp, double c_wp, bool fin, double c_fin) -> int {
-        QF_TRY(qf_launch_solve(ctx, ctx->poisson, from_state ? S[0].X : S[0].Xp, P, 1.0, skewh ? 1 : 0));
+        if (skewh) QF_TRY(qf_launch_hamiltonian(ctx, from_state ? S[0].X : S[0].Xp, P, 1.0));
+        else QF_TRY(qf_launch_solve(ctx, ctx->poisson, from_state ? S[0].X : S[0].Xp, P, 1.0, 0));
         // (P is complete before state 0's stage overwrites its stage argument; the other states need only P)
         for (int j = 0; j < k; ++j) {
             const cplx *Xarg = from_state ? S[j].X : S[j].Xp;
@@ -273,7 +275,10 @@ static int ns_setup(qf_ctx *ctx, ns_work &w)
 static int lu_hamiltonian(qf_ctx *ctx, ns_work &w, const cplx *Wt, double half_stepsize, const qf_isomp_hooks *hooks)
 {
     // (the Laplacian backend's select_skewherm flag picks the solve's branch, cpu.py:563-591)
-    if (!hooks || !hooks->hamiltonian) return qf_launch_solve(ctx, ctx->poisson, Wt, w.E, half_stepsize, (!hooks || hooks->solve_skewh) ? 1 : 0);
+    if (!hooks || !hooks->hamiltonian) {
+        if (!hooks || hooks->solve_skewh) return qf_launch_hamiltonian(ctx, Wt, w.E, half_stepsize);
+        return qf_launch_solve(ctx, ctx->poisson, Wt, w.E, half_stepsize, 0);
+    }
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     if (ctx->hook_host_bytes < mbytes) {
         for (int q = 0; q < 3; ++q) {
@@ -514,7 +519,9 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         for (int i = 0; i < maxit; ++i) {
             total_iterations += 1;
             // Phalf = vareps * Delta^-1 Whalf[0]   (+ Bhalf = vareps * Delta Thetahalf)
-            QF_TRY_R(qf_launch_solve(ctx, ctx->poisson, S[0].Xhalf, ctx->Phalf, vareps, 1));
+            // (magmp's Hamiltonian is solve_mhd: Poisson as such; a stack of isomp states follows the flow's)
+            if (magnetic) QF_TRY_R(qf_launch_solve(ctx, ctx->poisson, S[0].Xhalf, ctx->Phalf, vareps, 1));
+            else QF_TRY_R(qf_launch_hamiltonian(ctx, S[0].Xhalf, ctx->Phalf, vareps));
             if (magnetic) {
                 QF_TRY_R(qf_launch_laplace(ctx, S[1].Xhalf, Bhalf));
                 QF_TRY_R(qf_launch_lincomb(ctx, vareps, Bhalf, 0.0, nullptr, 0.0, Bhalf));

@@ -412,7 +412,9 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
                 }
                 if (magnetic) QF_HIP(hipMemcpyAsync(Bhalf, hP + NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
             } else {
-                QF_TRY(qf_launch_solve(ctx, ctx->poisson, S[0].Whalf, ctx->Phalf, vareps, hooks->solve_skewh ? 1 : 0));
+                // (the flow's Hamiltonian: an installed one in the skew-Hermitian, non-magnetic mode -- magmp's is solve_mhd)
+                if (hooks->solve_skewh && !magnetic) QF_TRY(qf_launch_hamiltonian(ctx, S[0].Whalf, ctx->Phalf, vareps));
+                else QF_TRY(qf_launch_solve(ctx, ctx->poisson, S[0].Whalf, ctx->Phalf, vareps, hooks->solve_skewh ? 1 : 0));
                 if (magnetic) {      // solve_mhd (mhd.py:10-18): B = laplace(Theta)
                     QF_TRY(qf_launch_laplace(ctx, S[1].Whalf, Bhalf));
                     QF_TRY(qf_launch_lincomb(ctx, vareps, Bhalf, 0.0, nullptr, 0.0, Bhalf));

@@ -361,6 +361,15 @@ struct qf_ctx {
     unsigned long long factor_clock = 0;
     size_t factor_budget_bytes = (size_t)512 << 20;
     double *lap_user = nullptr;
+    // the installed Hamiltonian P = T^-1 (W - F) of the flow (qf_set_hamiltonian): a factor pair of the context's own -- not
+    // in user_factors, so the cache above never recycles it -- and the offset matrix F, both allocated on first use and kept
+    // (with the key and fingerprint of what they hold) when the Hamiltonian is cleared; ham_table / ham_offset_on say what
+    // is in force.  Neither set: the built-in Delta^-1 W (ctx->poisson).
+    qf_factors ham;
+    unsigned long long ham_key = 0, ham_fp = 0;
+    cplx *ham_offset = nullptr;
+    unsigned long long ham_offset_key = 0, ham_offset_fp = 0;
+    bool ham_table = false, ham_offset_on = false;
 
     // spherical-harmonics transforms (quantization.hip): basis resident in HBM, m-major staging
     double *basis = nullptr;     // N(N+1)(2N+1)/6 doubles (quantization.py:68-113), uploaded once
@@ -460,6 +469,10 @@ int qf_launch_build_factors(qf_ctx *ctx, const double *lap_dev, qf_factors f);
 int qf_launch_solve(qf_ctx *ctx, const qf_factors &f, const cplx *W, cplx *P, double scale, int skewh,
                     qf_guard guard = qf_guard(), const qf_decide *dec = nullptr);
 int qf_launch_decide(qf_ctx *ctx, const qf_decide &dec);      // the deferred decision alone (end of a call)
+// P = scale * hamiltonian(W) for the stream matrix of the flow: ctx->poisson, or the factors / offset qf_set_hamiltonian
+// installed (k_solve_off with an offset); skew-Hermitian solve.  Poisson meant as such stays qf_launch_solve(ctx->poisson).
+int qf_launch_hamiltonian(qf_ctx *ctx, const cplx *W, cplx *P, double scale, qf_guard guard = qf_guard(),
+                          const qf_decide *dec = nullptr);
 int qf_launch_laplace(qf_ctx *ctx, const cplx *P, cplx *W);
 
 // complex64 data: float32 tables, float32 arithmetic (quflow/laplacian/cpu.py:725)

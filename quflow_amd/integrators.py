@@ -12,6 +12,7 @@ The whole call -- Poisson solves, both complex GEMMs, the fused commutator epilo
 residual norms and the W update -- runs in hand-written HIP kernels behind one C-ABI
 call (qf_isomp).  There is no CPU path: without the library or a GPU this raises.
 """
+import contextlib
 import ctypes
 import operator
 
@@ -100,6 +101,29 @@ def _is_native_hamiltonian(h):
         mod.startswith("quflow.laplacian") or mod.startswith("quflow_amd.laplacian"))
 
 
+def _installable(h, W):
+    """`h` if it is a TridiagonalHamiltonian that this call installs on its device context -- skew-Hermitian mode,
+    complex128 data -- else None (the instance is then the foreign callable it also is)."""
+    if (_laplacian.installable(h) and _SKEW_HERM_ and isinstance(W, np.ndarray) and W.dtype == np.complex128):
+        h.check_size(W.shape[-1])
+        return h
+    return None
+
+
+@contextlib.contextmanager
+def _hamiltonian_on(ctx, ham):
+    """The call's Hamiltonian installed on its context for the call alone: the cached per-N contexts are shared, and a
+    later default call must find the built-in Hamiltonian again -- also after an error."""
+    if ham is None:
+        yield
+        return
+    ham.install(ctx)
+    try:
+        yield
+    finally:
+        ham.uninstall(ctx)
+
+
 def isomp_fixedpoint(W,
                      dt,
                      steps=100,
@@ -139,7 +163,9 @@ def isomp_fixedpoint(W,
     assert minit >= 1, "minit must be at least 1."
     assert maxit >= minit, "maxit must be at minit."
 
-    native = _is_native_hamiltonian(hamiltonian)
+    # a TridiagonalHamiltonian is followed on the device (installed for this call): native in every route below
+    ham = _installable(hamiltonian, W)
+    native = ham is not None or _is_native_hamiltonian(hamiltonian)
     # `for k in range(steps)` and the in-place complex updates (isospectral.py:463, 481-482, 592): a float step count and a real
     # or integer W are TypeErrors, a negative count an empty loop -- a real W is not silently advanced and truncated here either
     steps = _reference_args(W, steps)
@@ -152,17 +178,17 @@ def isomp_fixedpoint(W,
         # hooks that act inside an iteration, the general (not skew-Hermitian) commutator, and hooks /
         # compsum on stacks: device-resident state with host hooks (qf_isomp_hooked)
         return _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_splitting, stats, callback,
-                             tol, maxit, minit, verbatim, compsum, reinitialize, device)
+                             tol, maxit, minit, verbatim, compsum, reinitialize, device, ham=ham)
     if hooks:
         return _isomp_stepwise(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim,
-                               compsum, reinitialize, device)
+                               compsum, reinitialize, device, ham=ham)
 
     if not isinstance(W, np.ndarray):
         raise TypeError("W must be a numpy ndarray")
     if W.ndim == 3 and W.shape[-1] == W.shape[-2]:
         # a stack of states: P from state 0, the exit test on state 0 (isospectral.py:527-532)
         return _isomp_states(W, dt, steps, tol, minit, maxit, reinitialize, False, stats, verbatim, device,
-                             tol_key='tol_auto', maxit_key='number_of_maxit')
+                             tol_key='tol_auto', maxit_key='number_of_maxit', ham=ham)
     if W.ndim != 2 or W.shape[0] != W.shape[1]:
         raise ValueError("W must be a square matrix or a (k,N,N) stack")
     N = W.shape[-1]
@@ -182,10 +208,11 @@ def isomp_fixedpoint(W,
         _lib.check(ctx._lib.qf_c64_download_W(ctx.handle, ptr(Wc)))
     else:
         Wc = np.ascontiguousarray(W, dtype=np.complex128)
-        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-        _lib.check(ctx._lib.qf_isomp(ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit),
-                                     int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(st)))
-        _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
+        with _hamiltonian_on(ctx, ham):
+            _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+            _lib.check(ctx._lib.qf_isomp(ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit),
+                                         int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(st)))
+            _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     if Wc is not W:
         W[...] = Wc                  # in-place contract
 
@@ -230,7 +257,22 @@ def _device_tol(W, dt, tol, compsum):
 
 
 def _isomp_stepwise(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
-                    reinitialize, device):
+                    reinitialize, device, ham=None):
+    if ham is None:
+        return _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
+                                  reinitialize, device)
+    if not isinstance(W, np.ndarray) or W.ndim != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError("W must be a square matrix")
+    if isinstance(tol, str) and tol != 'auto':
+        raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
+    # (an installed TridiagonalHamiltonian: the same loop, on the same stepper context, with it in force)
+    with _hamiltonian_on(get_stepper_context(W.shape[-1], device), ham):
+        return _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
+                                  reinitialize, device)
+
+
+def _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
+                       reinitialize, device):
     """strang_splitting / callback around device steps (built-in Hamiltonian): one step per
     qf_isomp / qf_isomp_continue call, the tolerance fixed once from the initial state as in the
     reference (isospectral.py:440-452)."""
@@ -435,7 +477,7 @@ class _HookTable:
 
 
 def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_splitting, stats, callback, tol,
-                  maxit, minit, verbatim, compsum, reinitialize, device):
+                  maxit, minit, verbatim, compsum, reinitialize, device, ham=None):
     """isomp_fixedpoint with hooks inside the iteration (forcing, foreign Hamiltonian), the general
     commutator, or hooks / compsum on a stack of states: qf_isomp_hooked keeps the trajectory on the
     device and calls back for what only Python can compute."""
@@ -468,9 +510,10 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
     ctx = get_stepper_context(N, device)
     st = _lib.IsompStats()
     tol_c, tol_report = _device_tol(W, dt, tol, compsum)
-    rc = ctx._lib.qf_isomp_hooked(ctx.handle, ptr(Wc), k, float(dt), int(steps), tol_c, int(minit),
-                                  int(maxit), int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(table.c),
-                                  ctypes.byref(st))
+    with _hamiltonian_on(ctx, ham):       # (`native`: the device's own solve, of what is installed)
+        rc = ctx._lib.qf_isomp_hooked(ctx.handle, ptr(Wc), k, float(dt), int(steps), tol_c, int(minit),
+                                      int(maxit), int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(table.c),
+                                      ctypes.byref(st))
     table.check(rc)
     if Wc is not W:
         W[...] = Wc
@@ -532,7 +575,7 @@ def _magmp_hooked(W, dt, steps, hamiltonian, native_mhd, time, forcing, stats, c
 
 
 def _isomp_states(W, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats, verbatim, device,
-                  tol_key, maxit_key):
+                  tol_key, maxit_key, ham=None):
     """(k,N,N) isomp / magmp through qf_isomp_states; W overwritten and returned."""
     auto = isinstance(tol, str) or tol < 0
     tol_c, tol_report = _device_tol(W, dt, tol, False)
@@ -540,8 +583,9 @@ def _isomp_states(W, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats
     ctx = get_context(N, device)
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     st = _lib.IsompStats()
-    _lib.check(ctx._lib.qf_isomp_states(ctx.handle, ptr(Wc), int(k), float(dt), int(steps), tol_c, int(minit),
-                                        int(maxit), int(bool(reinitialize)), int(bool(magnetic)), ctypes.byref(st)))
+    with _hamiltonian_on(ctx, ham):
+        _lib.check(ctx._lib.qf_isomp_states(ctx.handle, ptr(Wc), int(k), float(dt), int(steps), tol_c, int(minit),
+                                            int(maxit), int(bool(reinitialize)), int(bool(magnetic)), ctypes.byref(st)))
     if Wc is not W:
         W[...] = Wc
     if auto:
@@ -637,9 +681,11 @@ def _check_device_stepper_args(W, hamiltonian, forcing):
         raise ValueError("W must be a square matrix")
 
 
-def _lu_needs_hook_table(hamiltonian):
-    """The plain entry points are the default case (built-in Hamiltonian, skew-Hermitian flags on); a foreign
-    Hamiltonian or select_skewherm(False) goes through the hooked ones, whose table carries the two flags."""
+def _lu_needs_hook_table(hamiltonian, ham=None):
+    """The plain entry points are the default case (built-in or installed Hamiltonian, skew-Hermitian flags on); a
+    foreign Hamiltonian or select_skewherm(False) goes through the hooked ones, whose table carries the two flags."""
+    if ham is not None:
+        return False
     return (not _is_native_hamiltonian(hamiltonian)) or not (_SKEW_HERM_ and _laplacian._SKEW_HERM_)
 
 
@@ -672,10 +718,12 @@ def isomp_quasinewton(W, dt, steps=100, hamiltonian=_laplacian.solve_poisson, fo
         tol_c = float(np.finfo(np.float32).eps * (dt / hbar(W.shape[-1])) * np.linalg.norm(W, np.inf))
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     st = _lib.IsompStats()
-    if not _lu_needs_hook_table(hamiltonian):
+    ham = _installable(hamiltonian, W)
+    if not _lu_needs_hook_table(hamiltonian, ham):
         ctx = get_context(W.shape[-1], kwargs.get("device"))
-        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-        _lib.check(ctx._lib.qf_isomp_quasinewton(ctx.handle, float(dt), int(steps), tol_c, int(maxit), ctypes.byref(st)))
+        with _hamiltonian_on(ctx, ham):
+            _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+            _lib.check(ctx._lib.qf_isomp_quasinewton(ctx.handle, float(dt), int(steps), tol_c, int(maxit), ctypes.byref(st)))
     else:
         # a foreign Hamiltonian (isospectral.py:207): called back once per pass on host copies; the linear solves and
         # the update stay on the device.  A context of its own: the hook may use the shared one.  With
@@ -707,10 +755,12 @@ def isomp_simple(W, dt, steps=100, hamiltonian=_laplacian.solve_poisson, forcing
     if steps == 0 and not np.issubdtype(W.dtype, np.complexfloating):
         return W                 # the reference's empty loop never touches a real / integer W
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
-    if not _lu_needs_hook_table(hamiltonian):
+    ham = _installable(hamiltonian, W)
+    if not _lu_needs_hook_table(hamiltonian, ham):
         ctx = get_context(W.shape[-1], kwargs.get("device"))
-        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-        _lib.check(ctx._lib.qf_isomp_simple(ctx.handle, float(dt), int(steps)))
+        with _hamiltonian_on(ctx, ham):
+            _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+            _lib.check(ctx._lib.qf_isomp_simple(ctx.handle, float(dt), int(steps)))
     else:
         # a foreign Hamiltonian (isospectral.py:286) and / or select_skewherm(False): the general branch (:303-314)
         ctx = get_stepper_context(W.shape[-1], kwargs.get("device"))
@@ -758,9 +808,11 @@ def _erk(method, W, dt, steps, hamiltonian, forcing, device=None):
     steps = _reference_args(W, steps)         # (erk.py: `for k in range(steps)`, in-place updates of W)
     if steps == 0 and not np.issubdtype(W.dtype, np.complexfloating):
         return W                 # the reference's empty loop never touches a real / integer W
+    # a TridiagonalHamiltonian without `forcing` is installed for the call (with `forcing` it is the foreign callable)
+    ham = _installable(hamiltonian, W) if forcing is None and _laplacian._SKEW_HERM_ and W.ndim in (2, 3) else None
     if W.ndim == 3 and W.shape[1] == W.shape[2]:
         # a stack of states: P from state 0, bracket(P, W) broadcast over the stack (erk.py with (k,N,N) input)
-        if forcing is not None or not _is_native_hamiltonian(hamiltonian):
+        if forcing is not None or not (ham is not None or _is_native_hamiltonian(hamiltonian)):
             if W.dtype != np.complex128:
                 raise NotImplementedError("forcing / foreign Hamiltonians need a complex128 state on the HIP path.")
             # hooks see the whole stack; a foreign Hamiltonian returns ONE (N,N) stream matrix (qf_erk_states_hooked)
@@ -780,23 +832,25 @@ def _erk(method, W, dt, steps, hamiltonian, forcing, device=None):
             return W
         ctx = get_context(W.shape[-1], device)
         Wc = np.ascontiguousarray(W, dtype=np.complex128)
-        _lib.check(ctx._lib.qf_erk_states(ctx.handle, ptr(Wc), int(W.shape[0]), _lib.ERK_METHODS[method], float(dt),
-                                          int(steps), int(_laplacian._SKEW_HERM_)))
+        with _hamiltonian_on(ctx, ham):
+            _lib.check(ctx._lib.qf_erk_states(ctx.handle, ptr(Wc), int(W.shape[0]), _lib.ERK_METHODS[method], float(dt),
+                                              int(steps), int(_laplacian._SKEW_HERM_)))
         if Wc is not W:
             W[...] = Wc
         return W
     if W.ndim != 2 or W.shape[0] != W.shape[1]:
         raise ValueError("W must be a square matrix or a (k,N,N) stack")
-    if forcing is not None or not _is_native_hamiltonian(hamiltonian):
+    if forcing is not None or not (ham is not None or _is_native_hamiltonian(hamiltonian)):
         if W.dtype != np.complex128:
             raise NotImplementedError("forcing / foreign Hamiltonians need a complex128 state on the HIP path.")
         return _erk_hooked(method, W, dt, steps, hamiltonian, forcing, device)
     ctx = get_context(W.shape[-1], device)
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
-    _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-    _lib.check(ctx._lib.qf_erk(ctx.handle, _lib.ERK_METHODS[method], float(dt), int(steps),
-                               int(_laplacian._SKEW_HERM_)))
-    _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
+    with _hamiltonian_on(ctx, ham):
+        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+        _lib.check(ctx._lib.qf_erk(ctx.handle, _lib.ERK_METHODS[method], float(dt), int(steps),
+                                   int(_laplacian._SKEW_HERM_)))
+        _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     if Wc is not W:
         W[...] = Wc                  # in-place contract (erk.py:56,110,156)
     return W
@@ -850,18 +904,46 @@ class DeviceTrajectory:
     semantics of one `integrator(W, dt, steps=...)` call of simulation.solve
     (quflow/simulation.py:782-798): dW restarts from zero (isospectral.py:430)."""
 
-    def __init__(self, W0, device=None):
+    def __init__(self, W0, device=None, hamiltonian=None):
+        """`hamiltonian`: None / solve_poisson for the built-in one, or a TridiagonalHamiltonian, which is installed on the
+        trajectory's private context for its whole life: advance, advance_erk and advance_lu follow it."""
         # a complex64 initial state makes a single-precision trajectory (float32 solve, complex64 products:
         # what the reference does with complex64 input); anything else is complex128
         self.c64 = np.asarray(W0).dtype == np.complex64 and _laplacian.single_precision_on_device()
         self.dtype = np.complex64 if self.c64 else np.complex128
         W0 = np.ascontiguousarray(W0, dtype=self.dtype)
         self.N = W0.shape[-1]
+        tridiagonal = isinstance(hamiltonian, _laplacian.TridiagonalHamiltonian)
+        if tridiagonal:
+            hamiltonian.check_size(self.N)
+            if self.c64 or not (_laplacian.installable(hamiltonian) and _SKEW_HERM_):
+                raise NotImplementedError("a resident TridiagonalHamiltonian needs complex128 data and the skew-Hermitian "
+                                          "mode (select_skewherm(True))")
+        elif not _is_native_hamiltonian(hamiltonian):
+            raise TypeError("DeviceTrajectory takes the built-in Hamiltonian or a TridiagonalHamiltonian; any other callable "
+                            "runs through isomp(..., hamiltonian=...)")
         # a private context: the trajectory owns its device state (the shared per-N context of
         # get_context() is scratch for the host-in/host-out entry points)
         self.ctx = Context(self.N, default_device() if device is None else device)
         self._lib = self.ctx._lib
+        self.hamiltonian = None
+        if tridiagonal:
+            try:
+                hamiltonian.install(self.ctx)
+            except Exception:
+                self.ctx.close()
+                raise
+            self.hamiltonian = hamiltonian
         _lib.check((self._lib.qf_c64_upload_W if self.c64 else self._lib.qf_upload_W)(self.ctx.handle, ptr(W0)))
+
+    def hamiltonian_energy(self):
+        """H = -inner_L2(P, W - F)/2 of the resident state with P = T^-1 (W - F) of the installed Hamiltonian (the built-in
+        one: energy_euler): the conserved energy of the flow when T is symmetric.  `diagnostics()` keeps reporting
+        energy_euler, the built-in Poisson energy, whatever is installed."""
+        self._double_only("hamiltonian_energy")
+        e = ctypes.c_double()
+        _lib.check(self._lib.qf_hamiltonian_energy(self.ctx.handle, ctypes.byref(e)))
+        return e.value
 
     def advance(self, dt, steps, tol='auto', maxit=10, minit=1, compsum=False, reinitialize=False, diagnostics=False):
         """`diagnostics=True`: energy_euler and enstrophy of the new state come back with the statistics
@@ -1062,8 +1144,8 @@ class DeviceEnsemble:
     results bit-identical to advancing it alone -- but one host loop feeds all their streams, so the
     GPU overlaps the replicas.  For ensembles with more seeds than GPUs (quflow_amd.ensemble)."""
 
-    def __init__(self, W0s, device=None):
-        self.members = [DeviceTrajectory(W0, device=device) for W0 in W0s]
+    def __init__(self, W0s, device=None, hamiltonian=None):
+        self.members = [DeviceTrajectory(W0, device=device, hamiltonian=hamiltonian) for W0 in W0s]
         if not self.members:
             raise ValueError("DeviceEnsemble needs at least one initial condition")
         if len({m.N for m in self.members}) != 1:

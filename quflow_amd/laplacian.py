@@ -9,6 +9,7 @@ Everything below runs hand-written HIP kernels through the C ABI
 """
 import collections
 import ctypes
+import zlib
 
 import numpy as np
 
@@ -216,20 +217,25 @@ def solve_heat(h_times_nu, W0):
 _globalqg_cache = _LRU(4)
 
 
-def solve_globalqg(W, gamma=1.0):
-    """Delta P + gamma Z P Z = W, quflow/laplacian/cpu.py:829-877: the Laplacian table with
-    (gamma/2)(z_i^2 + z_j^2) taken off its diagonal coefficient, z = hbar*(-s..s) the diagonal of
-    the third Cartesian generator (geometry.py:132-151,173-194); same device Thomas kernel."""
-    N = np.asarray(W).shape[-1]
+def _globalqg_table(N, gamma, dtype=np.float64):
+    """The (N,N,2) table of Delta + gamma Z . Z: the Laplacian table with (gamma/2)(z_i^2 + z_j^2) taken off its diagonal
+    coefficient, z = hbar*(-s..s) the diagonal of the third Cartesian generator (cpu.py:829-877)."""
+    dtype = np.dtype(dtype)
     def build():
         s = (N - 1) / 2
         zvec = _geometry.hbar(N) * np.arange(-s, s + 1)
-        tab = laplacian(N, bc=False, dtype=_real_dtype(W)).copy()
+        tab = laplacian(N, bc=False, dtype=dtype).copy()
         tab[:, :, 0] -= (gamma / 2.0) * zvec ** 2
         tab[:, :, 0] -= (gamma / 2.0) * zvec[:, np.newaxis] ** 2
         return tab
-    return _solve_with_table(_globalqg_cache.lookup((N, float(gamma), np.dtype(_real_dtype(W)).str), build),
-                             _table_key("gqg", N, float(gamma)), W)
+    return _globalqg_cache.lookup((N, float(gamma), dtype.str), build)
+
+
+def solve_globalqg(W, gamma=1.0):
+    """Delta P + gamma Z P Z = W, quflow/laplacian/cpu.py:829-877 (the table of `_globalqg_table`); same device Thomas
+    kernel."""
+    N = np.asarray(W).shape[-1]
+    return _solve_with_table(_globalqg_table(N, gamma, _real_dtype(W)), _table_key("gqg", N, float(gamma)), W)
 
 
 def solve_viscdamp(h, W0, nu=1e-4, alpha=0.01, force=None, theta=1):
@@ -294,3 +300,131 @@ class PoissonHIP:
     solve_poisson = staticmethod(solve_poisson)
     laplace = staticmethod(laplace)
     select_skewherm = staticmethod(select_skewherm)
+
+
+def coriolis(N, omega):
+    """The offset matrix of solid-body rotation with angular velocity `omega`: shr2mat of the function 2 omega cos(theta),
+    i.e. of the one real coefficient 2 omega / sqrt(3) at elm2ind(1, 0) -- the convention shr2fun inverts: a unit
+    coefficient there is the function sqrt(3) cos(theta) (the transforms carry the factor sqrt(4 pi) of Y_10 =
+    sqrt(3 / (4 pi)) cos(theta)).  Dense, diagonal, skew-Hermitian and trace-free; it is 2 omega X3, twice omega times the
+    matrix of the Cartesian coordinate function x3 = cos(theta) (cartesian_generators).  The basis element T_10 =
+    elmr2mat(1, 0, N) is written in its closed form i sqrt(12 / (N^2 - 1)) diag(k - (N-1)/2) (unit norm_L2, last entry
+    positive: the reference's orientation rule), so that no quantization basis -- N^3/3 doubles -- is needed for one
+    diagonal."""
+    N = int(N)
+    d = (np.arange(N, dtype=np.float64) - (N - 1) / 2) * np.sqrt(12.0 / (N * N - 1.0))
+    F = np.zeros((N, N), dtype=np.complex128)
+    F[np.arange(N), np.arange(N)] = (2.0 * float(omega) / np.sqrt(3.0)) * 1j * d
+    return F
+
+
+def _sample_key(tag, a):
+    """A 64-bit id of a host array for the library's caches: its shape and a CRC of up to 64 Ki entries spread over it
+    (the library's own fingerprint catches a key that comes back with other content)."""
+    flat = np.ascontiguousarray(a).reshape(-1).view(np.float64)
+    stride = max(1, flat.shape[0] // 65536)
+    crc = zlib.crc32(flat[::stride].tobytes()) ^ (zlib.crc32(flat[-1:].tobytes()) << 1)
+    return _table_key(tag, a.shape, int(crc))
+
+
+class TridiagonalHamiltonian:
+    """`hamiltonian=` of the steppers for P = T^-1 (W - F): T a tridiagonal operator given by its (N,N,2) coefficient
+    table (the layout of `laplacian(N)`: diagonal and coupling coefficient per entry), F an optional fixed offset matrix
+    (Coriolis term `coriolis(N, omega)`, topography, ...).  The flow on a rotating sphere, the global quasi-geostrophic
+    model and Charney-Hasegawa-Mima are instances:
+
+        H = TridiagonalHamiltonian.poisson(N, offset=coriolis(N, omega))          # Delta P = W - F
+        H = TridiagonalHamiltonian.globalqg(N, gamma, offset=...)                 # Delta P + gamma Z P Z = W - F
+        H = TridiagonalHamiltonian.shifted(N, -alpha, -1.0)                       # (Delta - alpha) P = W
+
+    isomp / isomp_fixedpoint, euler / heun / rk4, isomp_simple / isomp_quasinewton, DeviceTrajectory, DeviceEnsemble and
+    quflow_amd.solve recognise an instance and install it on the device context they run on (qf_set_hamiltonian): the
+    table is factorised once, the offset stays in HBM and is subtracted inside the solve kernel, and the trajectory never
+    visits the host.  That holds for complex128 data with the skew-Hermitian flags on; elsewhere (complex64, the general
+    commutator, magmp) an instance is the callable `H(W) -> P` it also is and takes the foreign-Hamiltonian route.
+
+    The offset must be EXACTLY skew-Hermitian (the skew-Hermitian solve reads the upper triangle of its right-hand side
+    only): ValueError otherwise."""
+
+    def __init__(self, table, offset=None):
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 3 or table.shape[0] != table.shape[1] or table.shape[2] != 2 or table.shape[0] < 2:
+            raise ValueError("table must be an (N,N,2) coefficient table, got shape %s" % (table.shape,))
+        self.N = int(table.shape[0])
+        self.table = table
+        self.builtin = False         # the table is the built-in Laplacian's: the context's own factors serve
+        self.offset = None
+        if offset is not None:
+            offset = np.ascontiguousarray(offset, dtype=np.complex128)
+            if offset.shape != (self.N, self.N):
+                raise ValueError("offset must be (%d, %d), got %s" % (self.N, self.N, offset.shape))
+            if not np.array_equal(offset, -offset.conj().T):
+                raise ValueError("offset must be exactly skew-Hermitian (F == -F^H entry by entry): project it with "
+                                 "F = (F - F^H) / 2 first")
+            self.offset = offset
+        self.table_key = _sample_key("ham_table", self.table)
+        self.offset_key = 0 if self.offset is None else _sample_key("ham_offset", self.offset)
+
+    @classmethod
+    def poisson(cls, N, offset=None):
+        """Delta P = W - F with the Laplacian of solve_poisson (bc=True): the built-in factors, plus an offset."""
+        self = cls(laplacian(int(N), bc=True), offset)
+        self.builtin = True
+        return self
+
+    @classmethod
+    def globalqg(cls, N, gamma, offset=None):
+        """Delta P + gamma Z P Z = W - F: the operator of solve_globalqg (cpu.py:829-877)."""
+        return cls(_globalqg_table(int(N), gamma), offset)
+
+    @classmethod
+    def shifted(cls, N, c0, c1, offset=None):
+        """(c0 I - c1 Delta) P = W - F, the table of solve_helmholtz / solve_heat / solve_viscdamp; Charney-Hasegawa-Mima
+        (Delta - alpha) P = W is c0 = -alpha, c1 = -1."""
+        return cls(_shifted_table(int(N), c0, c1), offset)
+
+    # ---- installing on a device context (the steppers and the device objects call these)
+    def check_size(self, N):
+        if int(N) != self.N:
+            raise ValueError("the Hamiltonian was built for N=%d, the state has N=%d" % (self.N, int(N)))
+
+    def install(self, ctx):
+        self.check_size(ctx.N)
+        _lib.check(ctx._lib.qf_set_hamiltonian(ctx.handle, None if self.builtin else ptr(self.table),
+                                               ctypes.c_ulonglong(self.table_key),
+                                               None if self.offset is None else ptr(self.offset),
+                                               ctypes.c_ulonglong(self.offset_key)))
+
+    @staticmethod
+    def uninstall(ctx):
+        if ctx.handle:
+            _lib.check(ctx._lib.qf_clear_hamiltonian(ctx.handle))
+
+    # ---- the reference's `hamiltonian(W) -> P` protocol
+    def __call__(self, W):
+        W = np.asarray(W)
+        if W.ndim >= 3:
+            W = select_first(W)
+        if W.ndim != 2 or W.shape[0] != W.shape[1]:
+            raise ValueError("W must be a square matrix, got shape %s" % (W.shape,))
+        self.check_size(W.shape[-1])
+        if not _SKEW_HERM_ or _is_c64(W):
+            # the general solve / complex64 data: the host-in, host-out table solve of W - F
+            rhs = W if self.offset is None else W - self.offset.astype(W.dtype, copy=False)
+            tab = self.table.astype(np.float32) if _is_c64(W) else self.table
+            return _solve_with_table(tab, self.table_key, rhs)
+        Wc = as_c128(W, "W")
+        ctx = get_context(self.N)
+        P = np.empty_like(Wc)
+        self.install(ctx)
+        try:
+            _lib.check(ctx._lib.qf_hamiltonian(ctx.handle, ptr(Wc), ptr(P)))
+        finally:
+            self.uninstall(ctx)
+        return P.astype(W.dtype, copy=False) if W.dtype == np.complex64 else P
+
+
+def installable(h):
+    """`h` is a TridiagonalHamiltonian and the process is in the mode in which the device follows an installed one: the
+    skew-Hermitian solve (select_skewherm(True), the default)."""
+    return isinstance(h, TridiagonalHamiltonian) and _SKEW_HERM_

@@ -527,7 +527,9 @@ def _device_resident_ok(integrator, kwargs):
     if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim")
            for k in kwargs):
         return False
-    return _int._is_native_hamiltonian(kwargs.get("hamiltonian")) and _int._SKEW_HERM_ and _lap._SKEW_HERM_
+    h = kwargs.get("hamiltonian")
+    # (a TridiagonalHamiltonian is installed on the resident trajectory's context: as native as the built-in one)
+    return (_int._is_native_hamiltonian(h) or isinstance(h, _lap.TridiagonalHamiltonian)) and _int._SKEW_HERM_ and _lap._SKEW_HERM_
 
 
 def _in_notebook():
@@ -633,8 +635,9 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
     tr = None
     # (a complex64 state makes a single-precision resident trajectory: float32 solve, complex64 products and the
     # float32 tolerance rule, exactly what isomp does with a complex64 host array)
-    if use_device and W.ndim == 2 and W.dtype in (np.complex128, np.complex64):
-        tr = _int.DeviceTrajectory(W)
+    ham = ikw.get('hamiltonian') if isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian) else None
+    if use_device and W.ndim == 2 and W.dtype in (np.complex128, np.complex64) and (ham is None or W.dtype == np.complex128):
+        tr = _int.DeviceTrajectory(W, hamiltonian=ham)
         adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "compsum", "reinitialize") if k in ikw}
     want_shr = any(isinstance(c, Simulation) and 'shr' in c.qutypes for c in (callback or ()))
     try:

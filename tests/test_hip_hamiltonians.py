@@ -1,0 +1,402 @@
+"""GPU tests of the device-resident tridiagonal Hamiltonians P = T^-1 (W - F): qf_set_hamiltonian, k_solve_off (the chunked
+Thomas solve that subtracts the offset while it loads), quflow_amd.TridiagonalHamiltonian / coriolis, and every stepper and
+device object that follows an installed Hamiltonian -- against the CPU oracle, which gets the same Hamiltonian as a plain
+function `f(W)` built from oracle.solve_poisson / solve_globalqg / solve_with_table applied to W - F.
+
+Conventions of tests/test_hip_hooks_large.py: dt = 0.25 hbar(N), data from oracle.make_W0 / make_W0_smooth with seed 0, two
+steps; state within STEP_TOL = 1e-11, iteration and maxit counts identical, tol_auto to rtol 1e-12; on the oracle alone no step
+ended by maxit and a step took >= 2 iterations (>= 5 on smooth data).  Every case prints its error and error / bar.
+(One floor is lower: Hamiltonian B on smooth data.  The global-QG operator with gamma = 50 damps the iteration, and the oracle
+takes 4.5 - 5.5 iterations per step there -- 4.5 at N = 63 -- so "at least 5" cannot hold for those cases whatever the device
+does; they assert the lower end of the oracle's own range, 4.5, which still is a long sequence next to white data's floor of 2.)
+
+Two Hamiltonians, both with a FULL-matrix offset (a wrong index or mirror in the kernel's offset read moves the result by
+2e-4 .. 1.7e-2, seven orders above the bar):
+  A = poisson,          F = coriolis(N, 0.1) + 0.1 make_W0_smooth(N, 7)
+  B = globalqg(50),     F = coriolis(N, 0.5) + 0.5 make_W0_smooth(N, 7)
+Sizes, each the smallest that reaches its code: 63 (L = 4, odd N, guarded 32x32 edge tiles), 257 (L = 8, deferred step end taken
+inside the solve), 513 (L = 16), 768 (L = 9 folded), 1024 (stream-K second product with fused step end), 1152 (L = 17 folded),
+2176 (L = 32; B on white data, one step: an oracle step takes seconds there).
+
+Residency: in every native case the instance is of a subclass whose __call__ raises -- the run succeeds only if the stepper
+never came back to the host for the Hamiltonian."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+STEP_TOL = 1e-11
+ERK_TOL = 1e-12
+EPS = np.finfo(np.float64).eps
+
+
+@pytest.fixture(scope="module")
+def qfa():
+    import quflow_amd
+    if quflow_amd.device_count() < 1:
+        pytest.fail("no HIP device visible: the gpu tests must run on the MI355X box")
+    return quflow_amd
+
+
+def maxabs(a, b):
+    return float(np.max(np.abs(np.asarray(a) - np.asarray(b))))
+
+
+def report(tag, err, bar):
+    print("%-52s err = %.3e   err/bar = %.3e" % (tag, err, err / bar))
+    return err
+
+
+# ----------------------------------------------------------------------------- data and Hamiltonians (made once, read only)
+_DATA = {}
+
+
+def _cached(key, make):
+    if key not in _DATA:
+        a = make()
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+        _DATA[key] = a
+    return _DATA[key]
+
+
+def white(oracle, N, seed=0):
+    return _cached(("white", N, seed), lambda: oracle.make_W0(N, seed))
+
+
+def smooth(oracle, N, seed=0):
+    return _cached(("smooth", N, seed), lambda: oracle.make_W0_smooth(N, seed))
+
+
+def offset(qfa, oracle, case, N):
+    c = {"A": 0.1, "B": 0.5}[case]
+    return _cached(("offset", case, N), lambda: qfa.coriolis(N, c) + c * smooth(oracle, N, 7))
+
+
+def resident_class(qfa):
+    """TridiagonalHamiltonian whose host evaluation raises: a run that needs it left the device."""
+    if "cls" not in _DATA:
+        class Resident(qfa.TridiagonalHamiltonian):
+            def __call__(self, W):
+                raise AssertionError("the stepper came back to the host for the Hamiltonian")
+        _DATA["cls"] = Resident
+    return _DATA["cls"]
+
+
+def shifted_table(oracle, N, c0, c1):
+    lap = oracle.laplacian(N, bc=False)
+    tab = lap.copy()
+    tab[:, :, 0] = c0
+    tab[:, :, 1] = 0.0
+    tab -= c1 * lap
+    return tab
+
+
+def hamiltonians(qfa, oracle, case, N, with_offset=True, cls=None):
+    """(device instance, oracle function) of one Hamiltonian.  The oracle function returns an arithmetic result or a fresh
+    array (solve_poisson hands back a cached buffer) and reduces a stack to its first state as solve_poisson does."""
+    cls = resident_class(qfa) if cls is None else cls
+    F = offset(qfa, oracle, case if case in ("A", "B") else "A", N) if with_offset else None
+
+    def rhs(W):
+        W0 = W[0] if W.ndim == 3 else W
+        return W0 if F is None else W0 - F
+    if case in ("A", "poisson"):
+        return cls.poisson(N, offset=F), (lambda W: oracle.solve_poisson(rhs(W)).copy())
+    if case in ("B", "globalqg"):
+        return cls.globalqg(N, 50.0, offset=F), (lambda W: oracle.solve_globalqg(rhs(W), gamma=50.0))
+    assert case == "shifted"
+    tab = shifted_table(oracle, N, -0.5, -1.0)
+    return cls.shifted(N, -0.5, -1.0, offset=F), (lambda W: oracle.solve_with_table(tab, rhs(W)))
+
+
+def check_isomp(qfa, oracle, tag, W0, dt, H, f, kw_dev=None, kw_cpu=None, min_its=2.0, steps=2):
+    kw_dev = {} if kw_dev is None else kw_dev
+    kw_cpu = kw_dev if kw_cpu is None else kw_cpu
+    sg, sc = {"iterations": 0.0}, {"iterations": 0.0}
+    Wc = oracle.isomp_fixedpoint(W0.copy(), dt, steps=steps, hamiltonian=f, stats=sc, **kw_cpu)
+    Wg = qfa.isomp(W0.copy(), dt, steps=steps, hamiltonian=H, stats=sg, **kw_dev)
+    err = report(tag, maxabs(Wg, Wc), STEP_TOL)
+    print("    iterations/step %.1f  maxit %.1f" % (sc["iterations"], sc["number_of_maxit"]))
+    assert sc["number_of_maxit"] == 0.0 and sc["iterations"] >= min_its, (tag, sc)
+    assert sg["iterations"] == sc["iterations"] and sg["number_of_maxit"] == sc["number_of_maxit"], (tag, sg, sc)
+    np.testing.assert_allclose(sg["tol_auto"], sc["tol_auto"], rtol=1e-12)
+    assert err <= STEP_TOL, (tag, err)
+    return Wg, Wc
+
+
+# ----------------------------------------------------------------------------- the fused stepper with an offset, every chunk class
+OFFSET_CASES = ([(c, N, d) for c in ("A", "B") for N in (63, 257, 513, 768) for d in ("white", "smooth")]
+                + [(c, N, "white") for c in ("A", "B") for N in (1024, 1152)] + [("B", 2176, "white")])
+
+
+@pytest.mark.parametrize("case,N,data", OFFSET_CASES)
+def test_isomp_with_offset_vs_oracle(qfa, oracle, case, N, data):
+    W0 = (white if data == "white" else smooth)(oracle, N)
+    H, f = hamiltonians(qfa, oracle, case, N)
+    check_isomp(qfa, oracle, "isomp %s %s N=%d" % (case, data, N), W0, 0.25 * qfa.hbar(N), H, f,
+                min_its=2.0 if data == "white" else (5.0 if case == "A" else 4.5), steps=1 if N == 2176 else 2)
+    plan = qfa.get_context(N).plan()
+    assert plan["laplacian_inverse"]["kernel"].startswith("k_solve_off<double"), plan["laplacian_inverse"]
+    assert plan["hamiltonian"] == "poisson"            # cleared behind the call
+
+
+# ----------------------------------------------------------------------------- without an offset
+@pytest.mark.parametrize("N", [257, 1024])
+def test_installed_poisson_is_the_default_call(qfa, oracle, N):
+    """TridiagonalHamiltonian.poisson(N): the same table, the same factors, the same kernels -- the same bits."""
+    W0 = white(oracle, N)
+    dt = 0.25 * qfa.hbar(N)
+    H = resident_class(qfa).poisson(N)
+    s0, s1 = {"iterations": 0.0}, {"iterations": 0.0}
+    Wd = qfa.isomp(W0.copy(), dt, steps=2, stats=s0)
+    Wh = qfa.isomp(W0.copy(), dt, steps=2, hamiltonian=H, stats=s1)
+    assert np.array_equal(Wd, Wh) and s0 == s1, (maxabs(Wd, Wh), s0, s1)
+
+
+@pytest.mark.parametrize("case", ["globalqg", "shifted"])
+def test_tables_without_offset_vs_oracle(qfa, oracle, case):
+    N = 513
+    H, f = hamiltonians(qfa, oracle, case, N, with_offset=False)
+    check_isomp(qfa, oracle, "isomp %s no offset N=%d" % (case, N), white(oracle, N), 0.25 * qfa.hbar(N), H, f)
+    assert qfa.get_context(N).plan()["laplacian_inverse"]["kernel"].startswith("k_solve<double")
+
+
+# ----------------------------------------------------------------------------- the other entry points, Hamiltonian A
+def forcing(P, W):
+    return -0.05 * W + 0.02 * P
+
+
+class Recorder:
+    def __init__(self):
+        self.rows = []
+
+    def __call__(self, W, dW):
+        self.rows.append([np.linalg.norm(W), np.linalg.norm(dW)])
+
+
+@pytest.mark.parametrize("entry", ["forcing", "strang", "callback", "stack"])
+def test_isomp_hooks_follow_the_installed_hamiltonian(qfa, oracle, entry):
+    N = 257
+    dt = 0.25 * qfa.hbar(N)
+    H, f = hamiltonians(qfa, oracle, "A", N)
+    tag = "isomp A %s N=%d" % (entry, N)
+    if entry == "forcing":                # the native branch of the hooked stepper
+        check_isomp(qfa, oracle, tag, white(oracle, N), dt, H, f, {"forcing": forcing})
+    elif entry == "strang":
+        check_isomp(qfa, oracle, tag, white(oracle, N), dt, H, f, {"strang_splitting": qfa.ViscDampStep(1e-3, 0.05)},
+                    {"strang_splitting": lambda h, W: oracle.solve_viscdamp(h, W, nu=1e-3, alpha=0.05)})
+    elif entry == "callback":
+        rg, rc = Recorder(), Recorder()
+        check_isomp(qfa, oracle, tag, white(oracle, N), dt, H, f, {"callback": rg}, {"callback": rc})
+        assert len(rg.rows) == len(rc.rows) == 2
+        np.testing.assert_allclose(np.array(rg.rows), np.array(rc.rows), rtol=1e-9)
+    else:
+        S0 = np.stack([white(oracle, N, 1), white(oracle, N, 2)])
+        Wg, _ = check_isomp(qfa, oracle, tag, S0, dt, H, f)
+        assert Wg.shape == (2, N, N)
+
+
+@pytest.mark.parametrize("N", [63, 257])
+@pytest.mark.parametrize("method", ["rk4", "isomp_simple"])
+def test_explicit_steppers_follow_the_installed_hamiltonian(qfa, oracle, method, N):
+    dt = 0.25 * qfa.hbar(N)
+    H, f = hamiltonians(qfa, oracle, "A", N)
+    W0 = white(oracle, N)
+    Wc = getattr(oracle, method)(W0.copy(), dt, 2, hamiltonian=f)
+    Wg = getattr(qfa, method)(W0.copy(), dt, 2, hamiltonian=H)
+    err = report("%s A N=%d" % (method, N), maxabs(Wg, Wc), ERK_TOL)
+    assert err <= ERK_TOL, err
+    # ... and the offset entered: the same call with the built-in Hamiltonian lands elsewhere
+    assert maxabs(getattr(qfa, method)(W0.copy(), dt, 2), Wc) > 1e3 * ERK_TOL
+
+
+# ----------------------------------------------------------------------------- device objects
+def test_device_trajectory_with_hamiltonian(qfa, oracle):
+    N = 257
+    dt = 0.25 * qfa.hbar(N)
+    H, f = hamiltonians(qfa, oracle, "A", N)
+    W0 = white(oracle, N)
+    Wc = W0.copy()
+    sc = [{"iterations": 0.0}, {"iterations": 0.0}]
+    for s in sc:
+        oracle.isomp_fixedpoint(Wc, dt, steps=2, hamiltonian=f, stats=s)
+    tr = qfa.DeviceTrajectory(W0, hamiltonian=H)
+    try:
+        sg = [tr.advance(dt, 2), tr.advance(dt, 2)]
+        err = report("DeviceTrajectory A 2 x advance(2) N=%d" % N, maxabs(tr.download(), Wc), STEP_TOL)
+        plan = tr.ctx.plan()
+    finally:
+        tr.ctx.close()
+    assert [s["iterations"] for s in sg] == [s["iterations"] for s in sc]
+    assert all(s["number_of_maxit"] == 0.0 for s in sc)
+    assert err <= STEP_TOL
+    assert plan["hamiltonian"] == {"table_key": None, "offset": True}, plan["hamiltonian"]
+
+
+def test_device_ensemble_members_equal_single_trajectories(qfa, oracle):
+    N = 257
+    dt = 0.25 * qfa.hbar(N)
+    H, _ = hamiltonians(qfa, oracle, "B", N)
+    W0s = [white(oracle, N, s) for s in (0, 1, 2)]
+    ens = qfa.DeviceEnsemble(W0s, hamiltonian=H)
+    try:
+        st = ens.advance(dt, 2)
+        got = ens.download()
+    finally:
+        ens.close()
+    for W0, Wg, s in zip(W0s, got, st):
+        tr = qfa.DeviceTrajectory(W0, hamiltonian=H)
+        try:
+            s1 = tr.advance(dt, 2)
+            W1 = tr.download()
+        finally:
+            tr.ctx.close()
+        assert np.array_equal(Wg, W1) and s["total_iterations"] == s1["total_iterations"]
+        assert maxabs(W1, W0) > 1e-6
+
+
+def test_solve_stays_resident(qfa, oracle):
+    N = 257
+    dt = 0.25 * qfa.hbar(N)
+    H, _ = hamiltonians(qfa, oracle, "A", N)
+    W0 = white(oracle, N)
+    Ws = qfa.solve(W0.copy(), dt=dt, steps=4, steps_out=2, hamiltonian=H, progress_bar=False)
+    Wi = W0.copy()
+    qfa.isomp(Wi, dt, steps=2, hamiltonian=H)
+    qfa.isomp(Wi, dt, steps=2, hamiltonian=H)
+    assert np.array_equal(Ws, Wi), maxabs(Ws, Wi)
+
+
+# ----------------------------------------------------------------------------- nothing leaks into a later default call
+def test_installed_hamiltonian_does_not_leak(qfa, oracle):
+    N = 257
+    dt = 0.25 * qfa.hbar(N)
+    H, _ = hamiltonians(qfa, oracle, "A", N)
+    W, W2 = white(oracle, N), white(oracle, N, 3)
+
+    def defaults():
+        return (qfa.isomp(W2.copy(), dt, steps=2), qfa.isomp(W2.copy(), dt, steps=2, forcing=forcing),
+                qfa.rk4(W2.copy(), dt, steps=2), qfa.solve_poisson(W2).copy())
+    before = defaults()
+    qfa.isomp(W.copy(), dt, steps=2, hamiltonian=H)
+    qfa.isomp(W.copy(), dt, steps=2, hamiltonian=H, forcing=forcing)
+    qfa.rk4(W.copy(), dt, steps=2, hamiltonian=H)
+    for a, b in zip(before, defaults()):
+        assert np.array_equal(a, b)
+    # ... also behind a call that raised (a non-finite state: the reference's ValueError of the exit test)
+    Wbad = W.copy()
+    Wbad[0, 1], Wbad[1, 0] = np.nan, np.nan
+    with pytest.raises(ValueError):
+        qfa.isomp(Wbad, dt, steps=2, hamiltonian=H)
+    with pytest.raises(ValueError):
+        qfa.isomp(Wbad.copy(), dt, steps=2, hamiltonian=H, forcing=forcing)
+    assert qfa.get_context(N).plan()["hamiltonian"] == "poisson"
+    for a, b in zip(before, defaults()):
+        assert np.array_equal(a, b)
+
+
+# ----------------------------------------------------------------------------- evaluation and energy
+@pytest.mark.parametrize("N", [63, 1025])
+@pytest.mark.parametrize("case", ["A", "B"])
+def test_evaluation_vs_oracle(qfa, oracle, case, N):
+    H, f = hamiltonians(qfa, oracle, case, N, cls=qfa.TridiagonalHamiltonian)
+    W = white(oracle, N)
+    Pc = f(W)
+    Pg = H(W)
+    bar = 1e-12 * N * float(np.abs(Pc).max())
+    err = report("H(W) %s N=%d" % (case, N), maxabs(Pg, Pc), bar)
+    assert err <= bar
+    assert np.array_equal(Pg, -Pg.conj().T)
+    # the offset is in it: H(W + F) is the operator alone applied to W
+    bare = qfa.TridiagonalHamiltonian.poisson(N) if H.builtin else qfa.TridiagonalHamiltonian(H.table)
+    assert maxabs(H(W + offset(qfa, oracle, case, N)), bare(W)) <= bar
+
+
+@pytest.mark.parametrize("case", ["A", "B", "poisson"])
+def test_hamiltonian_energy(qfa, oracle, case):
+    N = 257
+    with_offset = case != "poisson"
+    H, f = hamiltonians(qfa, oracle, case, N, with_offset=with_offset)
+    W = white(oracle, N)
+    D = W - offset(qfa, oracle, case, N) if with_offset else W
+    want = -oracle.inner_L2(f(W), D) / 2.0
+    tr = qfa.DeviceTrajectory(W, hamiltonian=H)
+    try:
+        got = tr.hamiltonian_energy()
+        euler = tr.diagnostics()[0]
+    finally:
+        tr.ctx.close()
+    print("energy %s: device %.15e oracle %.15e" % (case, got, want))
+    np.testing.assert_allclose(got, want, rtol=1e-10)
+    # diagnostics() keeps the Euler energy of the built-in Poisson solve
+    np.testing.assert_allclose(euler, oracle.energy_euler(W), rtol=1e-10)
+
+
+def test_energy_drift_no_worse_than_the_oracle(qfa, oracle):
+    """200 steps at N = 64 with B: the drift of H = -<P, W - F>/2 on the device against the oracle's, 5 % slack plus the
+    resolution of the instrument -- H is a sum of N^2 products formed in fp64: sqrt(N^2) eps sum |P_ij| |D_ij| / (2N)."""
+    N, chunks, n = 64, 10, 20
+    dt = 0.25 * qfa.hbar(N)
+    H, f = hamiltonians(qfa, oracle, "B", N)
+    F = offset(qfa, oracle, "B", N)
+    W0 = white(oracle, N)
+
+    def energy(W):
+        return -oracle.inner_L2(f(W), W - F) / 2.0
+    Wc = W0.copy()
+    Ec = [energy(Wc)]
+    for _ in range(chunks):
+        oracle.isomp_fixedpoint(Wc, dt, steps=n, hamiltonian=f)
+        Ec.append(energy(Wc))
+    tr = qfa.DeviceTrajectory(W0, hamiltonian=H)
+    try:
+        Eg = [tr.hamiltonian_energy()]
+        for _ in range(chunks):
+            tr.advance(dt, n)
+            Eg.append(tr.hamiltonian_energy())
+        Wg = tr.download()
+    finally:
+        tr.ctx.close()
+    dg = float(np.abs(np.array(Eg) - Eg[0]).max())
+    dc = float(np.abs(np.array(Ec) - Ec[0]).max())
+    res = N * EPS * float((np.abs(f(Wc)) * np.abs(Wc - F)).sum()) / (2.0 * N)
+    print("energy drift over %d steps: device %.3e oracle %.3e resolution %.3e   |W_dev - W_cpu| %.3e"
+          % (chunks * n, dg, dc, res, maxabs(Wg, Wc)))
+    assert dg <= 1.05 * dc + res, (dg, dc, res)
+
+
+# ----------------------------------------------------------------------------- the Coriolis matrix
+def test_coriolis_against_the_transforms(qfa, oracle):
+    N, Om = 64, 0.7
+    F = qfa.coriolis(N, Om)
+    assert np.count_nonzero(F - np.diag(np.diag(F))) == 0 and np.array_equal(F, -F.conj().T)
+    assert abs(np.trace(F)) <= 1e-13
+    omega = np.zeros(N * N)
+    # (a unit shr coefficient at (1, 0) is the function sqrt(3) cos(theta): tests/test_transforms_host.py)
+    omega[qfa.elm2ind(1, 0)] = 2.0 * Om / np.sqrt(3.0)
+    err = report("coriolis vs shr2mat N=%d" % N, maxabs(F, qfa.shr2mat(omega, N)), 1e-13)
+    assert err <= 1e-13
+    assert maxabs(F, omega[qfa.elm2ind(1, 0)] * qfa.elmr2mat(1, 0, N).toarray()) <= 1e-13
+    theta, _ = qfa.sphgrid(N)
+    err = report("shr2fun(omega) vs 2 Omega cos(theta)", maxabs(qfa.shr2fun(omega, N, berezin=False), 2.0 * Om * np.cos(theta)), 1e-12)
+    assert err <= 1e-12
+    err = report("Delta^-1 F vs -F/2", maxabs(qfa.TridiagonalHamiltonian.poisson(N)(F), -F / 2.0), 1e-12)
+    assert err <= 1e-12
+
+
+# ----------------------------------------------------------------------------- argument errors, before any launch
+def test_argument_errors(qfa, oracle):
+    N = 64
+    with pytest.raises(ValueError):
+        qfa.TridiagonalHamiltonian(np.zeros((N, N, 3)))
+    F = np.array(offset(qfa, oracle, "A", N))
+    F[3, 5] += 1e-14
+    with pytest.raises(ValueError):
+        qfa.TridiagonalHamiltonian.poisson(N, offset=F)
+    H, _ = hamiltonians(qfa, oracle, "A", N)
+    W = white(oracle, 63)
+    for call in (lambda: qfa.isomp(W.copy(), 0.1, 2, hamiltonian=H), lambda: qfa.rk4(W.copy(), 0.1, 2, hamiltonian=H),
+                 lambda: qfa.DeviceTrajectory(W, hamiltonian=H), lambda: qfa.TridiagonalHamiltonian.poisson(N)(W)):
+        with pytest.raises(ValueError):
+            call()
