@@ -214,6 +214,40 @@ int qf_isomp_quasinewton_hooked(qf_ctx *ctx, double dt, int steps, double tol, i
 int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
                     int reinitialize, int magnetic, qf_isomp_stats *stats_out);
 
+/* ---- the same stack RESIDENT on the device across calls: what qf_upload_W / qf_isomp / qf_download_W are to one state.
+ *      qf_states_upload makes the (k,N,N) complex128 stack resident (buffers of the context's own, kept until the context
+ *      is destroyed); qf_states_advance is one qf_isomp_states call on it without the transfers -- the same loop, the same
+ *      bits: dX restarts from zero per call, the exit test is state 0's, the finite check covers every state; magnetic != 0
+ *      (k == 2) is magmp.  qf_states_download copies the stack out (k must be the resident k).
+ *      Errors: QF_ERR_STATE when no stack is resident -- before the first upload, and after a host-in / host-out
+ *      qf_isomp_states call on the same context, which uses the stack's buffers as its scratch (the hooked steppers keep
+ *      buffers of their own and leave a resident stack alone); QF_ERR_INVALID for magnetic with k != 2, a member index out
+ *      of range, a k mismatch on download; QF_ERR_NONFINITE as qf_isomp_states (the stack then holds the states after the
+ *      last completed step; qf_states_upload starts afresh). ---- */
+int qf_states_upload(qf_ctx *ctx, const void *states_host, int k);
+int qf_states_download(qf_ctx *ctx, void *states_host, int k);
+int qf_states_advance(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize, int magnetic,
+                      qf_isomp_stats *stats_out);
+/* Member access: qf_states_select copies member j into the context's state W (device copy, no transfer), after which every
+ * entry point that takes a NULL host pointer for "the resident state" works on it -- qf_mat2shr, qf_shr2fun, qf_eigh_state,
+ * qf_rotate, qf_grad, qf_diagnostics; qf_states_store copies W back into member j. */
+int qf_states_select(qf_ctx *ctx, int j);
+int qf_states_store(qf_ctx *ctx, int j);
+/* out[2 j] = <X_j, X_0>, out[2 j + 1] = <X_j, X_j>/2 for the k members of the resident stack (2 k doubles): what a run
+ * of passive tracers logs next to qf_diagnostics of member 0. */
+int qf_states_inner(qf_ctx *ctx, double *out);
+/* Diagnostics of the resident MHD pair (W, Theta), k == 2, with <.,.> = inner_L2 (quflow/geometry.py:72-76):
+ *   out[0] Ek = -<W, Delta^-1 W>/2   out[1] Em = -<Theta, Delta Theta>/2   out[2] X = <W, Theta>   (cross-helicity)
+ *   out[3] A  = <Theta, Theta>/2     out[4] S  = <W, W>/2;                  the conserved Hamiltonian is Ek + Em.
+ * One Poisson solve, then one pass over W, P and Theta that applies the Laplacian's stencil on the fly and reduces in a
+ * fixed order (no float atomics: bit-reproducible).  Ek and S are qf_diagnostics' values for W and A its enstrophy for
+ * Theta, bit for bit. */
+int qf_mhd_diagnostics(qf_ctx *ctx, double out[5]);
+/* qf_states_advance (magnetic != 0) followed by qf_mhd_diagnostics of the new state, queued behind the last step under the
+ * call's closing synchronisation.  Same results as the two calls.  mhd_out == NULL: qf_states_advance. */
+int qf_states_advance_diag(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize, int magnetic,
+                           qf_isomp_stats *stats_out, double *mhd_out);
+
 /* ---- the stepper with HOST HOOKS: isomp_fixedpoint's `forcing`, foreign `hamiltonian`, `strang_splitting`,
  *      `callback` (isospectral.py:338-353, 403-423, 466-467, 488-492, 512-520, 547-551, 598-603), the
  *      general branch of select_skewherm(False) (:504-505), and all of them -- with compsum -- on

@@ -36,11 +36,12 @@ from .geometry import so3_generators, cartesian_generators, rotate, rotation_mat
 from .dynamics import blob, north_blob, project_el
 from .laplacian import (solve_poisson, laplace, PoissonHIP, solve_heat, solve_helmholtz, solve_viscdamp,
                         solve_globalqg, ViscDampStep, TridiagonalHamiltonian, coriolis)
-from .integrators import (isomp, isomp_fixedpoint, IsompHIP, DeviceTrajectory, DeviceEnsemble, euler, heun, rk4,
+from .integrators import (isomp, isomp_fixedpoint, IsompHIP, DeviceTrajectory, DeviceEnsemble, DeviceStackTrajectory,
+                          DeviceMHDTrajectory, euler, heun, rk4,
                           isomp_simple, isomp_quasinewton, magmp, magmp_fixedpoint, solve_mhd,
                           commutator, commutator_generic, commutator_skewherm, estimate_stepsize, project_skewherm)
 from .analysis import scale_decomposition
-from .physics import energy_euler, enstrophy, inner_Hm1, norm_Hm1, inner_H1, norm_H1, sectional_curvature
+from .physics import (energy_euler, mhd_diagnostics, energy_mhd, cross_helicity, magnetic_energy, enstrophy, inner_Hm1, norm_Hm1, inner_H1, norm_H1, sectional_curvature)
 from .context import get_context, set_device, release_contexts, guard_report
 from ._lib import QuflowHipError, device_count, device_info
 

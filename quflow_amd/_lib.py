@@ -118,6 +118,16 @@ SIGNATURES = {
     "qf_isomp_states": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(IsompStats)]),
+    "qf_states_upload": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "qf_states_download": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "qf_states_advance": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.POINTER(IsompStats)]),
+    "qf_states_advance_diag": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.POINTER(IsompStats), _dp]),
+    "qf_states_select": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "qf_states_store": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "qf_mhd_diagnostics": (ctypes.c_int, [_vp, _dp]),
+    "qf_states_inner": (ctypes.c_int, [_vp, _dp]),
     "qf_isomp_hooked": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(IsompHooks),
                                        ctypes.POINTER(IsompStats)]),

@@ -243,6 +243,9 @@ int qf_ctx_destroy(qf_ctx *ctx)
         if (e) (void)hipEventDestroy(e);
     for (cplx *p : ctx->multi)
         if (p) (void)hipFree(p);
+    for (cplx *p : ctx->stack)
+        if (p) (void)hipFree(p);
+    if (ctx->mhd_part) (void)hipFree(ctx->mhd_part);
     for (int q = 0; q < 4; ++q) {
         if (ctx->oz_planes[q]) (void)hipFree(ctx->oz_planes[q]);
         if (ctx->oz_scale[q]) (void)hipFree(ctx->oz_scale[q]);

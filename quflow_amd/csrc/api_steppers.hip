@@ -436,13 +436,60 @@ static int isomp_quasinewton_impl(qf_ctx *ctx, double dt, int steps, double tol,
 // branches): P comes from state 0 only (cpu.py:696-697), every state runs the same products, the
 // exit test uses state 0's residual (isospectral.py:527-532).  magnetic != 0 (k == 2): magmp,
 // quflow/integrators/mhd.py:235-456 with hamiltonian = solve_mhd (mhd.py:10-18): B = Delta Theta
-// and the vorticity state gets [B, Theta] on top.  Host in / host out; the iteration control is
+// and the vorticity state gets [B, Theta] on top.  The iteration control is
 // host-side (one scalar read-back per iteration, as the reference does): these are the secondary
 // steppers, their products (>= 4 per iteration) dwarf the read-back.
-int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
-                    int reinitialize, int magnetic, qf_isomp_stats *stats_out)
+// The loop is written once (states_body) on the stack's resident buffers ctx->stack: qf_isomp_states is upload + body +
+// download, qf_states_advance the body alone on a stack that qf_states_upload left there.
+}  // extern "C"
+
+namespace {
+
+int stack_reserve(qf_ctx *ctx, size_t need)
 {
-    QF_TRY(check_ctx(ctx));
+    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    while (ctx->stack.size() < need) {
+        cplx *p = nullptr;
+        QF_HIP(hipMalloc((void **)&p, mbytes));
+        ctx->stack.push_back(p);
+    }
+    return QF_OK;
+}
+
+int stack_upload(qf_ctx *ctx, const void *states_host, int k)
+{
+    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    QF_TRY(stack_reserve(ctx, (size_t)5 * k));
+    for (int j = 0; j < k; ++j)
+        QF_HIP(hipMemcpyAsync(ctx->stack[5 * j], (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
+    return QF_OK;
+}
+
+// P = Delta^-1 W (k_solve), then the five sums in one pass (k_mhd_sums), on their way to the pinned scalars
+int enqueue_mhd_diagnostics(qf_ctx *ctx)
+{
+    if (!ctx->mhd_part) QF_HIP(hipMalloc((void **)&ctx->mhd_part, (size_t)(5 * 1024 + 8) * sizeof(double)));
+    double *out = ctx->mhd_part + 5 * 1024;
+    QF_TRY(qf_launch_solve(ctx, ctx->poisson, ctx->stack[0], ctx->stage, 1.0, 1));
+    QF_TRY(qf_launch_mhd_sums(ctx, ctx->stack[0], ctx->stage, ctx->stack[5], ctx->mhd_part, out));
+    QF_HIP(hipMemcpyAsync(ctx->host_scalars, out, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return QF_OK;
+}
+
+// (the forms of qf_diagnostics: -(<W,P>/N)/2 and (<W,W>/N)/2, inner_L2 = sum / N)
+void mhd_from_sums(const qf_ctx *ctx, double out[5])
+{
+    const int N = ctx->N;
+    const double *h = ctx->host_scalars;
+    out[0] = -(h[0] / N) / 2.0;      // Ek = -<W, Delta^-1 W>/2
+    out[1] = -(h[1] / N) / 2.0;      // Em = -<Theta, Delta Theta>/2
+    out[2] = h[2] / N;               // X  = <W, Theta>
+    out[3] = (h[3] / N) / 2.0;       // A  = <Theta, Theta>/2
+    out[4] = (h[4] / N) / 2.0;       // S  = <W, W>/2
+}
+
+int states_check_args(int minit, int maxit)
+{
     if (minit < 1) {
         qf_set_error("minit must be at least 1.");
         return QF_ERR_INVALID;
@@ -451,39 +498,38 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         qf_set_error("maxit must be at minit.");
         return QF_ERR_INVALID;
     }
-    if (!states_host || k < 1 || steps < 0 || (magnetic && k != 2)) {
-        qf_set_error("qf_isomp_states: bad arguments (k=%d, steps=%d, magnetic=%d)", k, steps, magnetic);
-        return QF_ERR_INVALID;
-    }
+    return QF_OK;
+}
+
+// `steps` steps of the k states in ctx->stack[5 j]: dX restarts from zero, the exit test is state 0's, the finite check covers
+// every state.  states_host != nullptr: the result is downloaded there;  mhd_out != nullptr (magnetic): the diagnostics of
+// the new state -- either one under the closing synchronisation.
+int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit, int reinitialize,
+                int magnetic, qf_isomp_stats *stats_out, double *mhd_out)
+{
     const int N = ctx->N;
     const size_t NN = (size_t)N * N, mbytes = NN * sizeof(cplx);
     const double hb = qf_hbar(N);
     const double vareps = dt / (2 * hb);
     // per state: X, dX[2], Xhalf, PXc;  magnetic: Bhalf, BT, BTP
-    const size_t need = (size_t)5 * k + (magnetic ? 3 : 0);
-    while (ctx->multi.size() < need) {
-        cplx *p = nullptr;
-        QF_HIP(hipMalloc((void **)&p, mbytes));
-        ctx->multi.push_back(p);
-    }
+    QF_TRY(stack_reserve(ctx, (size_t)5 * k + (magnetic ? 3 : 0)));
     const int slots32 = (N + 31) / 32;
     if (!ctx->multi_rowpart) QF_HIP(hipMalloc((void **)&ctx->multi_rowpart, (size_t)2 * slots32 * N * sizeof(double)));   // (sized as hooks.hip sizes it)
     struct st { cplx *X, *dX[2], *Xhalf, *PXc; int cur; };
     std::vector<st> S((size_t)k);
     for (int j = 0; j < k; ++j) {
-        S[j].X = ctx->multi[5 * j];
-        S[j].dX[0] = ctx->multi[5 * j + 1];
-        S[j].dX[1] = ctx->multi[5 * j + 2];
-        S[j].Xhalf = ctx->multi[5 * j + 3];
-        S[j].PXc = ctx->multi[5 * j + 4];
+        S[j].X = ctx->stack[5 * j];
+        S[j].dX[0] = ctx->stack[5 * j + 1];
+        S[j].dX[1] = ctx->stack[5 * j + 2];
+        S[j].Xhalf = ctx->stack[5 * j + 3];
+        S[j].PXc = ctx->stack[5 * j + 4];
         S[j].cur = 0;
-        QF_HIP(hipMemcpyAsync(S[j].X, (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
         QF_HIP(hipMemsetAsync(S[j].dX[0], 0, mbytes, ctx->stream));                          // dW = zeros_like(W)
         QF_HIP(hipMemcpyAsync(S[j].Xhalf, S[j].X, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    cplx *Bhalf = magnetic ? ctx->multi[5 * k] : nullptr;
-    cplx *BT = magnetic ? ctx->multi[5 * k + 1] : nullptr;
-    cplx *BTP = magnetic ? ctx->multi[5 * k + 2] : nullptr;
+    cplx *Bhalf = magnetic ? ctx->stack[5 * k] : nullptr;
+    cplx *BT = magnetic ? ctx->stack[5 * k + 1] : nullptr;
+    cplx *BTP = magnetic ? ctx->stack[5 * k + 2] : nullptr;
 
     // the upper-triangle second product wants every state exactly skew-Hermitian
     bool tri = ctx->gemm_tri_allowed && ctx->sk_partial && N >= ctx->gemm_tri_min_n;
@@ -523,8 +569,7 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
             if (magnetic) QF_TRY_R(qf_launch_solve(ctx, ctx->poisson, S[0].Xhalf, ctx->Phalf, vareps, 1));
             else QF_TRY_R(qf_launch_hamiltonian(ctx, S[0].Xhalf, ctx->Phalf, vareps));
             if (magnetic) {
-                QF_TRY_R(qf_launch_laplace(ctx, S[1].Xhalf, Bhalf));
-                QF_TRY_R(qf_launch_lincomb(ctx, vareps, Bhalf, 0.0, nullptr, 0.0, Bhalf));
+                QF_TRY_R(qf_launch_laplace_scaled(ctx, S[1].Xhalf, Bhalf, vareps));      // (one launch, the bits of laplace + lincomb)
             }
             for (int j = 0; j < k; ++j)                                   // Pstatecomm = Phalf @ statehalf
                 QF_TRY_R(qf_launch_zgemm(ctx, ctx->Phalf, S[j].Xhalf, S[j].PXc, nullptr));
@@ -596,12 +641,17 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         if (magnetic)
             QF_TRY_R(qf_launch_magnetic_update(ctx, BT, S[0].X, reinitialize ? nullptr : S[0].dX[S[0].cur], S[0].Xhalf));
     }
-    for (int j = 0; j < k; ++j)
-        QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-    QF_HIP(hipStreamSynchronize(ctx->stream));
 #undef QF_TRY_R
     ctx->gemm_tri = tri_saved;
     ctx->gemm_tri32 = tri32_saved;
+    // what the caller queues behind the last step rides on the call's closing synchronisation: the MHD diagnostics
+    // (qf_states_advance_diag) or the download (qf_isomp_states)
+    if (mhd_out) QF_TRY(enqueue_mhd_diagnostics(ctx));
+    if (states_host)
+        for (int j = 0; j < k; ++j)
+            QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    if (mhd_out) mhd_from_sums(ctx, mhd_out);
     if (stats_out) {
         stats_out->total_iterations = total_iterations;
         stats_out->number_of_maxit = number_of_maxit;
@@ -611,5 +661,149 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
     return QF_OK;
 }
 
+
+}  // namespace
+
+extern "C" {
+
+int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
+                    int reinitialize, int magnetic, qf_isomp_stats *stats_out)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(states_check_args(minit, maxit));
+    if (!states_host || k < 1 || steps < 0 || (magnetic && k != 2)) {
+        qf_set_error("qf_isomp_states: bad arguments (k=%d, steps=%d, magnetic=%d)", k, steps, magnetic);
+        return QF_ERR_INVALID;
+    }
+    ctx->stack_k = 0;        // (host in / host out: the stack's buffers are this call's scratch)
+    QF_TRY(stack_upload(ctx, states_host, k));
+    return states_body(ctx, states_host, k, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats_out, nullptr);
+}
+
+// ---- the resident stack --------------------------------------------------------------------------------------
+int qf_states_upload(qf_ctx *ctx, const void *states_host, int k)
+{
+    QF_TRY(check_ctx(ctx));
+    if (!states_host || k < 1) {
+        qf_set_error("qf_states_upload: bad arguments (k=%d)", k);
+        return QF_ERR_INVALID;
+    }
+    ctx->stack_k = 0;
+    QF_TRY(stack_upload(ctx, states_host, k));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->stack_k = k;
+    return QF_OK;
+}
+
+static int need_stack(const qf_ctx *ctx, const char *who)
+{
+    if (ctx->stack_k < 1) {
+        qf_set_error("%s: no stack is resident (qf_states_upload; a host-in / host-out qf_isomp_states call discards it)", who);
+        return QF_ERR_STATE;
+    }
+    return QF_OK;
+}
+
+int qf_states_download(qf_ctx *ctx, void *states_host, int k)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(need_stack(ctx, "qf_states_download"));
+    if (!states_host || k != ctx->stack_k) {
+        qf_set_error("qf_states_download: bad arguments (k=%d, resident %d)", k, ctx->stack_k);
+        return QF_ERR_INVALID;
+    }
+    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    for (int j = 0; j < k; ++j)
+        QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, ctx->stack[5 * j], mbytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
+int qf_states_advance_diag(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize, int magnetic,
+                           qf_isomp_stats *stats_out, double *mhd_out)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(states_check_args(minit, maxit));
+    QF_TRY(need_stack(ctx, "qf_states_advance"));
+    if (steps < 0 || (magnetic && ctx->stack_k != 2) || (mhd_out && !magnetic)) {
+        qf_set_error("qf_states_advance: bad arguments (resident k=%d, steps=%d, magnetic=%d)", ctx->stack_k, steps, magnetic);
+        return QF_ERR_INVALID;
+    }
+    return states_body(ctx, nullptr, ctx->stack_k, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats_out, mhd_out);
+}
+
+int qf_states_advance(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize, int magnetic,
+                      qf_isomp_stats *stats_out)
+{
+    return qf_states_advance_diag(ctx, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats_out, nullptr);
+}
+
+static int stack_member(qf_ctx *ctx, int j, const char *who)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(need_stack(ctx, who));
+    if (j < 0 || j >= ctx->stack_k) {
+        qf_set_error("%s: member %d of a stack of %d", who, j, ctx->stack_k);
+        return QF_ERR_INVALID;
+    }
+    return QF_OK;
+}
+
+int qf_states_select(qf_ctx *ctx, int j)
+{
+    QF_TRY(stack_member(ctx, j, "qf_states_select"));
+    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    QF_HIP(hipMemcpyAsync(ctx->W, ctx->stack[5 * j], mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->w_skew_known = false;       // (as after qf_upload_W)
+    ctx->increment_valid = false;
+    return QF_OK;
+}
+
+int qf_states_store(qf_ctx *ctx, int j)
+{
+    QF_TRY(stack_member(ctx, j, "qf_states_store"));
+    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    QF_HIP(hipMemcpyAsync(ctx->stack[5 * j], ctx->W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return QF_OK;
+}
+
+int qf_states_inner(qf_ctx *ctx, double *out)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(need_stack(ctx, "qf_states_inner"));
+    if (!out) {
+        qf_set_error("qf_states_inner: null output");
+        return QF_ERR_INVALID;
+    }
+    // k_inner2 per member (the launch of qf_diagnostics), 32 members per read-back of the pinned scalars
+    const int N = ctx->N, k = ctx->stack_k;
+    for (int j0 = 0; j0 < k; j0 += 32) {
+        const int n = k - j0 < 32 ? k - j0 : 32;
+        for (int j = 0; j < n; ++j) {
+            QF_TRY(qf_launch_inner2(ctx, ctx->stack[5 * (j0 + j)], ctx->stack[0], ctx->scalars + 2));
+            QF_HIP(hipMemcpyAsync(ctx->host_scalars + 2 * j, ctx->scalars + 2, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        QF_HIP(hipStreamSynchronize(ctx->stream));
+        for (int j = 0; j < n; ++j) {
+            out[2 * (j0 + j)] = ctx->host_scalars[2 * j] / N;
+            out[2 * (j0 + j) + 1] = (ctx->host_scalars[2 * j + 1] / N) / 2.0;
+        }
+    }
+    return QF_OK;
+}
+
+int qf_mhd_diagnostics(qf_ctx *ctx, double out[5])
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(need_stack(ctx, "qf_mhd_diagnostics"));
+    if (!out || ctx->stack_k != 2) {
+        qf_set_error("qf_mhd_diagnostics: the resident stack must be the pair (W, Theta) (k=%d)", ctx->stack_k);
+        return QF_ERR_INVALID;
+    }
+    QF_TRY(enqueue_mhd_diagnostics(ctx));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    mhd_from_sums(ctx, out);
+    return QF_OK;
+}
 
 }  // extern "C"

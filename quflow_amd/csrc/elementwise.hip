@@ -745,7 +745,66 @@ __global__ __launch_bounds__(256) void k_inner2(size_t n, const C *__restrict__ 
     }
 }
 
+// The five sums of the MHD diagnostics (quflow/integrators/mhd.py's invariants with inner_L2) in one pass over W,
+// P = Delta^-1 W and Theta; Delta Theta is formed in the pass from the stencil (qf_laplace_entry: k_laplace's bits), so no
+// B matrix is written.  Grid, stride loop, wave_sum, per-block partials and the last block's fold in fixed order are
+// k_inner2's -- the additions of a sum happen in the order of k_inner2's (its four loads in flight add in the order of this
+// plain loop), so sum Re(W conj P) and sum |W|^2 are qf_diagnostics' of W and sum |Theta|^2 is qf_diagnostics' of Theta,
+// bit for bit.  No float atomics.  out: [0] <W,P>  [1] <Theta, Delta Theta>  [2] <W,Theta>  [3] <Theta,Theta>  [4] <W,W>
+__global__ __launch_bounds__(256) void k_mhd_sums(int N, const cplx *__restrict__ W, const cplx *__restrict__ P,
+                                                   const cplx *__restrict__ Theta, double *__restrict__ partial, unsigned *ticket,
+                                                   double *__restrict__ out)
+{
+    __shared__ double part[5][4];
+    __shared__ int last;
+    const unsigned n = (unsigned)N * (unsigned)N;      // (N <= 8192: N^2 <= 2^26)
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const unsigned stride = gridDim.x * 256u;
+    for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < n; e += stride) {
+        const int i = (int)(e / (unsigned)N), j = (int)(e - (unsigned)i * (unsigned)N);
+        const cplx w = W[e], p = P[e], t = Theta[e];
+        const cplx lt = qf_laplace_entry<double, cplx>(N, Theta, i, j);
+        s[0] += re_dot_d(w, p);
+        s[1] += re_dot_d(t, lt);
+        s[2] += re_dot_d(w, t);
+        s[3] += re_dot_d(t, t);
+        s[4] += re_dot_d(w, w);
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        s[q] = wave_sum(s[q]);
+        if ((threadIdx.x & 63) == 0) part[q][threadIdx.x >> 6] = s[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q)
+            __hip_atomic_store(partial + 1024 * q + blockIdx.x, (part[q][0] + part[q][1]) + (part[q][2] + part[q][3]), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        last = last_block_of_launch(ticket, blockIdx.x, gridDim.x) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!last || threadIdx.x >= 64) return;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        double f = 0.0;
+        for (int b = threadIdx.x; b < (int)gridDim.x; b += 64) f += __hip_atomic_load(partial + 1024 * q + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        f = wave_sum(f);
+        if (threadIdx.x == 0) out[q] = f;
+    }
+}
+
 }  // namespace
+
+int qf_launch_mhd_sums(qf_ctx *ctx, const cplx *W, const cplx *P, const cplx *Theta, double *part, double *out_dev)
+{
+    const size_t n = (size_t)ctx->N * ctx->N;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 1024) blocks = 1024;       // (k_inner2's grid; the group counters are its own: launches of one stream never overlap)
+    hipLaunchKernelGGL(k_mhd_sums, dim3(blocks), dim3(256), 0, ctx->stream, ctx->N, W, P, Theta, part, ctx->ticket + 640, out_dev);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
 
 int qf_launch_call_begin(qf_ctx *ctx, double tol, int minit, int maxit, int auto_tol, double tol_factor)
 {

@@ -57,24 +57,6 @@ __device__ unsigned long long *qf_probe_stamps = nullptr;  // [blocks*waves][16]
 
 namespace {
 
-__device__ __forceinline__ double lap_b(int N, int i, int j)
-{
-    // cpu.py:82  -((N-1)(2k+1+|m|) - 2k(k+|m|)),  k = min(i,j), |m| = |j-i|
-    long long k = i < j ? i : j;
-    long long am = i < j ? j - i : i - j;
-    long long NN = N;
-    return -(double)((NN - 1) * (2 * k + 1 + am) - 2 * k * (k + am));
-}
-
-__device__ __forceinline__ double lap_a(int N, int i, int j)
-{
-    // cpu.py:83  sqrt(((k+|m|)(N-k-|m|)) (k(N-k)))  (exact integer under the root for N <= 8192)
-    long long k = i < j ? i : j;
-    long long am = i < j ? j - i : i - j;
-    long long NN = N;
-    return sqrt((double)(((k + am) * (NN - k - am)) * (k * (NN - k))));
-}
-
 // R = float: the reference's float32 table for complex64 input (cpu.py:55-95 with dtype=float32, cpu.py:725):
 // the integer-valued diagonal cast to float32 (exact below 2^24), the double-precision square root rounded
 // to float32, the boundary condition subtracted in float32.
@@ -84,10 +66,10 @@ __global__ void k_lap_table(int N, int bc, R *__restrict__ lap)
     size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (size_t)N * N) return;
     int i = (int)(e / N), j = (int)(e % N);
-    R b = (R)lap_b(N, i, j);
+    R b = (R)qf_lap_b(N, i, j);
     if (bc && e == 0) b -= R(0.5);  // cpu.py:90
     lap[2 * e] = b;
-    lap[2 * e + 1] = (R)lap_a(N, i, j);
+    lap[2 * e + 1] = (R)qf_lap_a(N, i, j);
 }
 
 // One thread per flat walk t = 0..N; sequential (runs once per table).
@@ -125,26 +107,18 @@ __global__ void k_laplace(int N, const C2 *__restrict__ P, C2 *__restrict__ W)
     int j = blockIdx.x * blockDim.x + threadIdx.x;
     int i = blockIdx.y;
     if (j >= N) return;
-    size_t e = (size_t)i * N + j;
-    R b = (R)lap_b(N, i, j);
-    C2 p = P[e];
-    R wr = b * p.x, wi = b * p.y;
-    if (i < N - 1 && j < N - 1) {
-        R a = (R)lap_a(N, i + 1, j + 1);
-        C2 q = P[e + N + 1];
-        wr += a * q.x;
-        wi += a * q.y;
-    }
-    if (i > 0 && j > 0) {
-        R a = (R)lap_a(N, i, j);
-        C2 q = P[e - N - 1];
-        wr += a * q.x;
-        wi += a * q.y;
-    }
-    C2 o;
-    o.x = wr;
-    o.y = wi;
-    W[e] = o;
+    W[(size_t)i * N + j] = qf_laplace_entry<R, C2>(N, P, i, j);
+}
+
+// W = scale * (Delta P): magmp's Bhalf = vareps * Delta Thetahalf without the second pass.  The stencil sum is rounded as
+// k_laplace rounds it, then multiplied once (what k_lincomb does to k_laplace's output: same bits).
+__global__ void k_laplace_scaled(int N, const double2 *__restrict__ P, double2 *__restrict__ W, double scale)
+{
+    int j = blockIdx.x * blockDim.x + threadIdx.x;
+    int i = blockIdx.y;
+    if (j >= N) return;
+    const double2 o = qf_laplace_entry<double, double2>(N, P, i, j);
+    W[(size_t)i * N + j] = make_double2(scale * o.x, scale * o.y);
 }
 
 // ---- real-type traits: the solve is instantiated for double (complex128 data) and float (complex64 data: the
@@ -549,6 +523,15 @@ int qf_launch_laplace(qf_ctx *ctx, const cplx *P, cplx *W)
     const int N = ctx->N;
     dim3 block(256), grid((N + 255) / 256, N);
     hipLaunchKernelGGL((k_laplace<double, double2>), grid, block, 0, ctx->stream, N, P, W);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+int qf_launch_laplace_scaled(qf_ctx *ctx, const cplx *P, cplx *W, double scale)
+{
+    const int N = ctx->N;
+    dim3 block(256), grid((N + 255) / 256, N);
+    hipLaunchKernelGGL(k_laplace_scaled, grid, block, 0, ctx->stream, N, P, W, scale);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }

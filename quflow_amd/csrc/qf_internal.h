@@ -186,6 +186,52 @@ __device__ __forceinline__ double qf_modulus(double er, double ei)
     g = __builtin_fma(d, h, g);
     return (x > 0.0 && x < __builtin_inf()) ? g : x;     // (0 -> 0, inf -> inf, NaN -> NaN)
 }
+
+// Coefficients of Delta_N (quflow/laplacian/cpu.py:82-83), recomputed where they are used: no table traffic.
+__device__ __forceinline__ double qf_lap_b(int N, int i, int j)
+{
+    // cpu.py:82  -((N-1)(2k+1+|m|) - 2k(k+|m|)),  k = min(i,j), |m| = |j-i|
+    long long k = i < j ? i : j;
+    long long am = i < j ? j - i : i - j;
+    long long NN = N;
+    return -(double)((NN - 1) * (2 * k + 1 + am) - 2 * k * (k + am));
+}
+__device__ __forceinline__ double qf_lap_a(int N, int i, int j)
+{
+    // cpu.py:83  sqrt(((k+|m|)(N-k-|m|)) (k(N-k)))  (exact integer under the root for N <= 8192)
+    long long k = i < j ? i : j;
+    long long am = i < j ? j - i : i - j;
+    long long NN = N;
+    return sqrt((double)(((k + am) * (NN - k - am)) * (k * (NN - k))));
+}
+// (Delta P)[i,j] by _dot_cpu_generic, cpu.py:98-108: every kernel that applies the stencil calls THIS function -- k_laplace,
+// its scaled form and k_mhd_sums -- so they agree bit for bit.  Products and sums are separate roundings (no FMA), in the
+// reference's order: diagonal, then the entry below-right, then the one above-left.
+template <typename R, typename C2>
+__device__ __forceinline__ C2 qf_laplace_entry(int N, const C2 *__restrict__ P, int i, int j)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)i * N + j;
+    R b = (R)qf_lap_b(N, i, j);
+    C2 p = P[e];
+    R wr = b * p.x, wi = b * p.y;
+    if (i < N - 1 && j < N - 1) {
+        R a = (R)qf_lap_a(N, i + 1, j + 1);
+        C2 q = P[e + N + 1];
+        wr += a * q.x;
+        wi += a * q.y;
+    }
+    if (i > 0 && j > 0) {
+        R a = (R)qf_lap_a(N, i, j);
+        C2 q = P[e - N - 1];
+        wr += a * q.x;
+        wi += a * q.y;
+    }
+    C2 o;
+    o.x = wr;
+    o.y = wi;
+    return o;
+}
 #endif
 
 // ---- complex64 data (single.hip; poisson.hip instantiates the solve for float): the float32 working set of a
@@ -340,8 +386,14 @@ struct qf_ctx {
     unsigned *oz_tflags = nullptr; // launch epoch per upper-triangle tile: "its tile is in oz_tbuf"
     unsigned oz_epoch = 0;
     double *oz_diag = nullptr;     // [N] Im (Phalf @ Whalf)_ii formed in fp64 by the slicing launch (ozaki.hip, PAIR)
-    std::vector<cplx *> multi;   // per-state buffers of qf_isomp_states (allocated on demand, kept)
+    std::vector<cplx *> multi;   // scratch matrices of the hooked steppers (hooks.hip), qf_erk_states and the LU steppers (on demand, kept)
     double *multi_rowpart = nullptr;
+    // the (k,N,N) stack of qf_isomp_states and of the resident qf_states_* entry points (api_steppers.hip): per state
+    // X, dX[2], Xhalf, PXc, then magmp's Bhalf, BT, BTP -- buffers of their own (allocated on demand, kept), which the
+    // users of `multi` above never write.  stack_k > 0: a stack of that many states is resident in stack[5 j].
+    std::vector<cplx *> stack;
+    int stack_k = 0;
+    double *mhd_part = nullptr;  // k_mhd_sums: 5 x 1024 block partials, then the five sums (on demand)
     cplx *hook_host[3] = {nullptr, nullptr, nullptr};   // pinned staging of the hooked steppers (hooks.hip), on demand
     size_t hook_host_bytes = 0;
     cplx *ns_inv = nullptr;  // Newton-Schulz inverse of I - E (isomp_simple / isomp_quasinewton), on demand
@@ -474,6 +526,9 @@ int qf_launch_decide(qf_ctx *ctx, const qf_decide &dec);      // the deferred de
 int qf_launch_hamiltonian(qf_ctx *ctx, const cplx *W, cplx *P, double scale, qf_guard guard = qf_guard(),
                           const qf_decide *dec = nullptr);
 int qf_launch_laplace(qf_ctx *ctx, const cplx *P, cplx *W);
+// W = scale * (Delta P) in one launch: the stencil sum is rounded first, then multiplied once -- the bits of
+// qf_launch_laplace followed by qf_launch_lincomb(scale, W, 0, nullptr, 0, W)
+int qf_launch_laplace_scaled(qf_ctx *ctx, const cplx *P, cplx *W, double scale);
 
 // complex64 data: float32 tables, float32 arithmetic (quflow/laplacian/cpu.py:725)
 int qf_launch_lap_table(qf_ctx *ctx, int bc, float *lap_dev);
@@ -658,6 +713,9 @@ int qf_launch_call_begin(qf_ctx *ctx, double tol, int minit, int maxit, int auto
 // out_dev[0] = sum Re(A conj(B)), out_dev[1] = sum |A|^2 in one pass
 template <class C> int qf_launch_inner2(qf_ctx *ctx, const C *A, const C *B, double *out_dev);
 int qf_launch_inner(qf_ctx *ctx, const cplx *A, const cplx *B, double *out_dev);  // sum Re(A conj(B))
+// the five sums of the MHD diagnostics in one pass over W, P = Delta^-1 W and Theta (part: 5 x 1024 doubles of block partials):
+// out_dev[0..4] = sum Re(W conj P), sum Re(Theta conj(Delta Theta)), sum Re(W conj Theta), sum |Theta|^2, sum |W|^2
+int qf_launch_mhd_sums(qf_ctx *ctx, const cplx *W, const cplx *P, const cplx *Theta, double *part, double *out_dev);
 // explicit Runge-Kutta stage on the products A = P@X, B = X@P (B == nullptr: B = A^H, skew-Hermitian case)
 int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, double inv_hb, const cplx *W, cplx *acc,
                         double c_acc, cplx *Wp, double c_wp, cplx *Wout, double c_fin);

@@ -1138,6 +1138,145 @@ class DeviceTrajectory:
         _lib.check(self._lib.qf_sync(self.ctx.handle))
 
 
+MHD_KEYS = ("energy_kinetic", "energy_magnetic", "cross_helicity", "magnetic_casimir", "enstrophy")
+
+
+def _mhd_dict(out):
+    """qf_mhd_diagnostics' five values by name; `energy` = Ek + Em is the conserved Hamiltonian."""
+    d = dict(zip(MHD_KEYS, (float(v) for v in out)))
+    d["energy"] = d["energy_kinetic"] + d["energy_magnetic"]
+    return d
+
+
+def _check_stack(states, magnetic, N=None):
+    """The (k,N,N) complex128 stack a resident stack trajectory takes, C-contiguous; ValueError otherwise."""
+    states = np.asarray(states)
+    if states.ndim != 3:
+        raise ValueError("a stack of states must be a (k,N,N) array, got shape %s" % (states.shape,))
+    if states.shape[0] < 1 or states.shape[1] != states.shape[2]:
+        raise ValueError("the members of a stack must be square matrices, got shape %s" % (states.shape,))
+    if states.dtype != np.complex128:
+        raise ValueError("a resident stack is complex128, got %s" % states.dtype)
+    if magnetic and states.shape[0] != 2:
+        raise ValueError("the MHD state must be a (2,N,N) array (W, Theta), got shape %s" % (states.shape,))
+    if N is not None and states.shape[-1] != N:
+        raise ValueError("state must be (k, %d, %d), got %s" % (N, N, states.shape))
+    return np.ascontiguousarray(states)
+
+
+class DeviceStackTrajectory:
+    """Keeps a (k,N,N) stack resident in HBM across chunks: what DeviceTrajectory is to one state.  Each `advance` has
+    the semantics, and the bits, of one `isomp(stack, dt, steps=...)` call (state 0 drives the flow, the others are carried
+    along; isospectral.py:463-611 on a 3-D W) or, with `magnetic=True` on the pair (W, Theta), of one
+    `magmp(state, dt, steps=...)` call (mhd.py:235-456 with hamiltonian = solve_mhd): dX restarts from zero per call.
+    Skew-Hermitian mode, complex128, the built-in Hamiltonian."""
+
+    def __init__(self, states0, magnetic=False, device=None):
+        states0 = _check_stack(states0, magnetic)
+        if not (_SKEW_HERM_ and _laplacian._SKEW_HERM_):
+            raise NotImplementedError("a resident stack needs the skew-Hermitian mode (select_skewherm(True))")
+        self.magnetic = bool(magnetic)
+        self.k, self.N = states0.shape[0], states0.shape[-1]
+        self.dtype = np.complex128
+        # a private context: the trajectory owns its device state (as DeviceTrajectory)
+        self.ctx = Context(self.N, default_device() if device is None else device)
+        self._lib = self.ctx._lib
+        # member access: a DeviceTrajectory's resident helpers on this context's state W, where qf_states_select puts member j
+        self._member = DeviceTrajectory.__new__(DeviceTrajectory)
+        self._member.N, self._member.c64, self._member.dtype = self.N, False, np.complex128
+        self._member.ctx, self._member._lib, self._member.hamiltonian = self.ctx, self._lib, None
+        try:
+            _lib.check(self._lib.qf_states_upload(self.ctx.handle, ptr(states0), self.k))
+        except Exception:
+            self.ctx.close()
+            raise
+
+    def advance(self, dt, steps, tol='auto', maxit=10, minit=1, reinitialize=False, diagnostics=False):
+        """The keys of DeviceTrajectory.advance; `diagnostics=True` adds `diagnostics()` of the new state -- for MHD queued
+        behind the last step under the call's closing synchronisation (qf_states_advance_diag)."""
+        assert minit >= 1, "minit must be at least 1."
+        assert maxit >= minit, "maxit must be at minit."
+        tol_c = -1.0 if isinstance(tol, str) else float(tol)
+        st = _lib.IsompStats()
+        args = (self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit), int(bool(reinitialize)),
+                int(self.magnetic), ctypes.byref(st))
+        out = {}
+        if diagnostics and self.magnetic:
+            d = (ctypes.c_double * 5)()
+            _lib.check(self._lib.qf_states_advance_diag(*args, d))
+            out = _mhd_dict(d)
+        else:
+            _lib.check(self._lib.qf_states_advance(*args))
+            if diagnostics:
+                out = self.diagnostics()
+        out.update({"iterations": st.total_iterations / max(steps, 1),
+                    "number_of_maxit": st.number_of_maxit / max(steps, 1),
+                    "total_iterations": st.total_iterations, "tol": st.tol_used,
+                    "last_resnorm": st.last_resnorm})
+        return out
+
+    def diagnostics(self):
+        """MHD: energy_kinetic = -<W, Delta^-1 W>/2, energy_magnetic = -<Theta, Delta Theta>/2, energy (their sum, the
+        conserved Hamiltonian), cross_helicity = <W, Theta>, magnetic_casimir = <Theta, Theta>/2, enstrophy = <W, W>/2 --
+        one solve and one reduction pass on the device (qf_mhd_diagnostics).
+        A stack of tracers: energy and enstrophy of state 0 and `members`, one (<X_j, X_0>, <X_j, X_j>/2) per member."""
+        if self.magnetic:
+            d = (ctypes.c_double * 5)()
+            _lib.check(self._lib.qf_mhd_diagnostics(self.ctx.handle, d))
+            return _mhd_dict(d)
+        _lib.check(self._lib.qf_states_select(self.ctx.handle, 0))
+        e, s = self._member.diagnostics()
+        m = (ctypes.c_double * (2 * self.k))()
+        _lib.check(self._lib.qf_states_inner(self.ctx.handle, m))
+        return {"energy": e, "enstrophy": s, "members": [(m[2 * j], m[2 * j + 1]) for j in range(self.k)]}
+
+    def _select(self, j):
+        _lib.check(self._lib.qf_states_select(self.ctx.handle, int(j)))
+        return self._member
+
+    def shr(self, j, n_omega=None):
+        """DeviceTrajectory.shr of member j."""
+        return self._select(j).shr(n_omega)
+
+    def fun(self, j, n_omega=None, berezin=True):
+        """DeviceTrajectory.fun of member j."""
+        return self._select(j).fun(n_omega, berezin)
+
+    def spectrum(self, j):
+        """DeviceTrajectory.spectrum of member j: the invariant of the flow for every member of the stack."""
+        return self._select(j).spectrum()
+
+    def rotate(self, xi):
+        """Rotate every member in place, X_j <- R X_j R^H with R = exp(xi . S) (quflow_amd.geometry.rotate of each
+        downloaded member, bit for bit, without any transfer).  Returns self."""
+        for j in range(self.k):
+            self._select(j).rotate(xi)
+            _lib.check(self._lib.qf_states_store(self.ctx.handle, j))
+        return self
+
+    def download(self):
+        states = np.zeros((self.k, self.N, self.N), dtype=np.complex128)
+        _lib.check(self._lib.qf_states_download(self.ctx.handle, ptr(states), self.k))
+        return states
+
+    def upload(self, states):
+        """Replace the resident stack (e.g. after a call that ended in an error)."""
+        states = _check_stack(states, self.magnetic, self.N)
+        if states.shape[0] != self.k:
+            raise ValueError("state must be (%d, %d, %d), got %s" % (self.k, self.N, self.N, states.shape))
+        _lib.check(self._lib.qf_states_upload(self.ctx.handle, ptr(states), self.k))
+
+    def sync(self):
+        _lib.check(self._lib.qf_sync(self.ctx.handle))
+
+
+class DeviceMHDTrajectory(DeviceStackTrajectory):
+    """The MHD pair (W, Theta) resident on the device: DeviceStackTrajectory(state0, magnetic=True)."""
+
+    def __init__(self, state0, device=None):
+        super().__init__(state0, magnetic=True, device=device)
+
+
 class DeviceEnsemble:
     """k independent trajectories resident on ONE GPU, advanced together (qf_isomp_multi): each
     member is a DeviceTrajectory of its own -- own Hamiltonian, own exit decisions, own statistics,

@@ -31,6 +31,41 @@ def enstrophy(W):
     return _diagnostics(W)[1]
 
 
+def mhd_diagnostics(state):
+    """The diagnostics of the MHD state (W, Theta), a (2,N,N) array, in one device call (qf_mhd_diagnostics: one Poisson
+    solve, one reduction pass): a dict with energy_kinetic = -<W, Delta^-1 W>/2, energy_magnetic = -<Theta, Delta Theta>/2,
+    energy = their sum (the conserved Hamiltonian of quflow/integrators/mhd.py's system), cross_helicity = <W, Theta>,
+    magnetic_casimir = <Theta, Theta>/2 and enstrophy = <W, W>/2.  DeviceMHDTrajectory.diagnostics() of a resident state."""
+    from .integrators import _mhd_dict
+    state = np.asarray(state)
+    if state.ndim != 3 or state.shape[0] != 2 or state.shape[1] != state.shape[2]:
+        raise ValueError("the MHD state must be a (2,N,N) array (W, Theta), got shape %s" % (state.shape,))
+    sc = np.ascontiguousarray(state, dtype=np.complex128)
+    ctx = get_context(sc.shape[-1])
+    _lib.check(ctx._lib.qf_states_upload(ctx.handle, ptr(sc), 2))
+    d = (ctypes.c_double * 5)()
+    _lib.check(ctx._lib.qf_mhd_diagnostics(ctx.handle, d))
+    return _mhd_dict(d)
+
+
+def energy_mhd(state):
+    """H = -<W, Delta^-1 W>/2 - <Theta, Delta Theta>/2 of the MHD state (W, Theta)."""
+    return mhd_diagnostics(state)["energy"]
+
+
+def cross_helicity(state):
+    """<W, Theta> of the MHD state (W, Theta)."""
+    return mhd_diagnostics(state)["cross_helicity"]
+
+
+def magnetic_energy(Theta):
+    """-<Theta, Delta Theta>/2 for the magnetic potential Theta, an (N,N) matrix."""
+    Theta = np.asarray(Theta)
+    if Theta.ndim != 2 or Theta.shape[0] != Theta.shape[1]:
+        raise ValueError("Theta must be a square matrix, got shape %s" % (Theta.shape,))
+    return mhd_diagnostics(np.stack([Theta, Theta]))["energy_magnetic"]
+
+
 def inner_Hm1(W1, W2):
     """-<W1, Delta^-1 W2>, quflow/physics.py:9-11."""
     from .geometry import inner_L2

@@ -532,6 +532,41 @@ def _device_resident_ok(integrator, kwargs):
     return (_int._is_native_hamiltonian(h) or isinstance(h, _lap.TridiagonalHamiltonian)) and _int._SKEW_HERM_ and _lap._SKEW_HERM_
 
 
+def _resident_kind(integrator, ikw, W):
+    """How `solve` may keep the run on the device between its chunks, from the stepper, its keyword arguments and the state:
+    'single' (DeviceTrajectory: what _device_resident_ok admits, on an (N,N) complex128 / complex64 state), 'stack'
+    (DeviceStackTrajectory: isomp on a (k,N,N) complex128 stack, built-in Hamiltonian, no compsum), 'mhd'
+    (DeviceMHDTrajectory: magmp with hamiltonian = solve_mhd on a (2,N,N) complex128 state) or None.  Pure: nothing is
+    created or touched."""
+    from . import integrators as _int
+    from . import laplacian as _lap
+    W = np.asarray(W)
+    if W.ndim == 2:
+        ham = isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian)
+        ok = (_device_resident_ok(integrator, ikw) and W.shape[0] == W.shape[1]
+              and W.dtype in (np.complex128, np.complex64) and (not ham or W.dtype == np.complex128))
+        return 'single' if ok else None
+    if W.ndim != 3 or W.shape[1] != W.shape[2] or W.dtype != np.complex128:
+        return None
+    if not (_int._SKEW_HERM_ and _lap._SKEW_HERM_):
+        return None
+    if ikw.get("forcing") is not None or ikw.get("callback") is not None:
+        return None
+    if integrator in (_int.magmp, _int.magmp_fixedpoint):
+        if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "reinitialize", "verbatim", "forcing", "callback")
+               for k in ikw):
+            return None
+        return 'mhd' if ikw.get("hamiltonian") is _int.solve_mhd and W.shape[0] == 2 else None
+    if integrator in (_int.isomp, _int.isomp_fixedpoint) or isinstance(integrator, _int.IsompHIP):
+        if ikw.get("strang_splitting") is not None or ikw.get("compsum"):
+            return None
+        if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim", "forcing",
+                         "callback", "strang_splitting") for k in ikw):
+            return None
+        return 'stack' if _int._is_native_hamiltonian(ikw.get("hamiltonian")) else None
+    return None
+
+
 def _in_notebook():
     try:
         from IPython import get_ipython
@@ -549,7 +584,8 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
     progress_bar / progress_file: the reference's tqdm progress display (simulation.py:764-780); never
     forwarded to the integrator.  inner_steps / inner_time: the deprecated names of steps_out / dt_out.
     resident: keep the trajectory on the device between the chunks (default: whenever the stepper is
-    quflow_amd.isomp with its built-in Hamiltonian and no host hooks, on a complex128 (N,N) state).
+    quflow_amd.isomp with its built-in Hamiltonian and no host hooks, on a complex128 (N,N) state or a
+    (k,N,N) stack, or quflow_amd.magmp with hamiltonian=solve_mhd on the (2,N,N) MHD state: _resident_kind).
     As in the reference the caller's array is advanced in place (isomp overwrites W) and the final
     state is returned."""
     from . import integrators as _int
@@ -639,6 +675,13 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
     if use_device and W.ndim == 2 and W.dtype in (np.complex128, np.complex64) and (ham is None or W.dtype == np.complex128):
         tr = _int.DeviceTrajectory(W, hamiltonian=ham)
         adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "compsum", "reinitialize") if k in ikw}
+    # a (k,N,N) stack under isomp, the MHD pair under magmp: resident too unless resident=False
+    stack_kind = _resident_kind(integrator, ikw, W) if (resident is None or resident) and W.ndim == 3 else None
+    if stack_kind in ('stack', 'mhd'):
+        tr = _int.DeviceStackTrajectory(W, magnetic=(stack_kind == 'mhd'))
+        adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "reinitialize") if k in ikw}
+    else:
+        stack_kind = None
     want_shr = any(isinstance(c, Simulation) and 'shr' in c.qutypes for c in (callback or ()))
     try:
         for k0 in range(0, steps, max(steps_out, 1)):
@@ -650,11 +693,12 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
                 if W_caller.flags.writeable:
                     W_caller[...] = W                  # the reference's stepper advances the caller's array in place
                 if 'stats' in ikw and ikw['stats']:
+                    # (the keys the host path fills: magmp's are 'tol' and 'maxit', mhd.py:341,452-454)
                     if isinstance(adv_kw.get("tol", 'auto'), str) or adv_kw.get("tol", -1) < 0:
-                        ikw['stats']['tol_auto'] = st["tol"]
+                        ikw['stats']['tol' if stack_kind == 'mhd' else 'tol_auto'] = st["tol"]
                     ikw['stats']['iterations'] = st["iterations"]
-                    ikw['stats']['number_of_maxit'] = st["number_of_maxit"]
-                if want_shr and not tr.c64:
+                    ikw['stats']['maxit' if stack_kind == 'mhd' else 'number_of_maxit'] = st["number_of_maxit"]
+                if want_shr and stack_kind is None and not tr.c64:
                     extra["device_shr"] = [tr.shr()]        # mat2shr on the resident state: N^2 doubles over PCIe
             else:
                 W = integrator(W, dt, steps=n, **ikw)
