@@ -121,6 +121,41 @@ int qf_hamiltonian(qf_ctx *ctx, const void *W_host, void *P_host);
 /* H = -inner_L2(P, W - F)/2 of the resident state, P = T^-1 (W - F): the conserved energy when T is symmetric */
 int qf_hamiltonian_energy(qf_ctx *ctx, double *H);
 
+/* ---- the forcing of the flow.  None by default.  Installed: the affine forcing
+ *          F(P, W) = F0 + a_W W + a_P P + a_lap Delta W      (a_* real, F0 a fixed N x N complex128 pattern)
+ * -- a fixed pattern, Rayleigh friction, a large-scale drag on the stream function and viscosity -- evaluated by one kernel
+ * (k_forcing_affine, csrc/hooks.hip) where a stepper's loop reaches `forcing(P, W)` (isospectral.py:512-520, 591-596;
+ * erk.py:47-49), instead of the host hook's PCIe round trip.  Where a loop evaluates it at a matrix X (Whalf in the isomp
+ * loop, the stage argument in the explicit ones) with the stream matrix Ph as the loop holds it, a stream-matrix scale
+ * pscale and an output scale s, the device computes per entry, on real and imaginary parts separately, every product and
+ * sum rounded on its own (no fused multiply-add):
+ *          p = Ph * pscale
+ *          f = F0[e]                     (0 when there is no F0)
+ *          f = f + a_W * X[e]            (term skipped entirely when a_W == 0.0)
+ *          f = f + a_P * p               (skipped when a_P == 0.0)
+ *          f = f + a_lap * (Delta X)[e]  (skipped when a_lap == 0.0; Delta X as qf_laplace forms it)
+ *          out = s * f
+ * isomp loop: pscale = 1 / (dt / (2 hbar)), s = dt / 2;  explicit loops and qf_forcing: pscale = s = 1 -- the roundings of
+ * the host-hook route, so a host callable that repeats the lines above gives the same trajectory bit for bit.
+ *   F0_host   N x N complex128, NULL = none; kept in a buffer the context owns.  Meant to be skew-Hermitian (the caller
+ *             checks; quflow_amd.AffineForcing does).
+ *   F0_key    caller-chosen id (0: always upload again).  A call that repeats the key AND the fingerprint (4096 sampled
+ *             entries) of what the context still holds does not upload again.
+ *   a_*       finite, else QF_ERR_INVALID.
+ * FOLLOW an installed forcing: qf_isomp_forced; qf_isomp_hooked with k = 1, not magnetic, and qf_erk_hooked -- both when
+ * their hook table has no `forcing` member (with one as well: QF_ERR_UNSUPPORTED); qf_forcing.
+ * REFUSE with QF_ERR_UNSUPPORTED while one is installed, rather than drop the force: qf_isomp / _continue / _diag / _multi,
+ * qf_c64_isomp / _continue / _multi, qf_isomp_states, qf_states_advance / _diag, qf_erk, qf_erk_states / _hooked,
+ * qf_isomp_simple / _quasinewton (plain and hooked), qf_isomp_hooked with k > 1 or magnetic.  compsum with an installed
+ * forcing: QF_ERR_UNSUPPORTED, "Compensated sum with forcing is not yet implemented." (isospectral.py:588-589). */
+int qf_set_forcing(qf_ctx *ctx, const void *F0_host, unsigned long long F0_key, double a_W, double a_P, double a_lap);
+int qf_clear_forcing(qf_ctx *ctx);          /* no forcing again (the buffer is kept) */
+/* F = F(P, W) of what is installed, pscale = s = 1; host in, host out.  QF_ERR_STATE when nothing is installed.
+ * All three pointers NULL: the kernel alone, queued on the context's stream without a synchronisation, on the resident
+ * state and the stream-matrix buffer as the last call left it, the result left on the device (timing between
+ * qf_timer_start / qf_timer_stop: tools/forcing_resident.py). */
+int qf_forcing(qf_ctx *ctx, const void *P_host, const void *W_host, void *F_host);
+
 /* ---- stepper protocol: isomp_fixedpoint (quflow/integrators/isospectral.py:338-613),
  *      called by simulation.solve (quflow/simulation.py:788) ---------------------- */
 int qf_upload_W(qf_ctx *ctx, const void *W_host);     /* host -> ctx state W */
@@ -289,6 +324,14 @@ typedef struct qf_isomp_hooks {
 /* states_host: (k,N,N) complex128, overwritten with the result.  compsum with forcing: QF_ERR_UNSUPPORTED (:588-589) */
 int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
                     int compsum, int reinitialize, const qf_isomp_hooks *hooks, qf_isomp_stats *stats_out);
+/* The loop of qf_isomp_hooked on the context's RESIDENT state (qf_upload_W / qf_download_W), with the forcing installed by
+ * qf_set_forcing (none installed: no force term) and the Hamiltonian installed by qf_set_hamiltonian: k = 1, skew-Hermitian
+ * branch, no host hook, no N^2 transfer in either direction.  strang_table != NULL: the half step W <- T^-1 W with that
+ * (N,N,2) table before and after every step, on the device (as the hook table's strang_table / strang_key members).
+ * The same bits as qf_isomp_hooked gives for the same state, forcing and half step; dW restarts from zero per call; one
+ * scalar is read back per iteration for the exit test.  Arguments otherwise as qf_isomp. */
+int qf_isomp_forced(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize,
+                    const double *strang_table, unsigned long long strang_key, qf_isomp_stats *stats_out);
 /* euler / heun / rk4 (erk.py:19-160) with `forcing(P, W)` and / or a foreign `hamiltonian(W)` (the `hamiltonian`,
  * `forcing`, `user` and `skewh` members of the hook table; k = 1).  W_host: (N,N), overwritten. */
 int qf_erk_hooked(qf_ctx *ctx, void *W_host, int method, double dt, int steps, const qf_isomp_hooks *hooks);

@@ -88,6 +88,11 @@ SIGNATURES = {
     "qf_clear_hamiltonian": (ctypes.c_int, [_vp]),
     "qf_hamiltonian": (ctypes.c_int, [_vp, _vp, _vp]),
     "qf_hamiltonian_energy": (ctypes.c_int, [_vp, _dp]),
+    "qf_set_forcing": (ctypes.c_int, [_vp, _vp, ctypes.c_ulonglong, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "qf_clear_forcing": (ctypes.c_int, [_vp]),
+    "qf_forcing": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "qf_isomp_forced": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, _vp, ctypes.c_ulonglong, ctypes.POINTER(IsompStats)]),
     "qf_factor_cache_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ulonglong)]),
     "qf_comm_unique_id": (ctypes.c_int, [_vp]),
     "qf_comm_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),

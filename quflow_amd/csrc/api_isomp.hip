@@ -711,6 +711,7 @@ int isomp_impl(qf_ctx *ctx, double dt, int steps, double tol, int minit, int max
         qf_set_error("qf_isomp: steps must be >= 0");
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, is_c64<S> ? "qf_c64_isomp" : "qf_isomp"));
     const bool dbg = getenv("QUFLOW_HIP_DEBUG") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms_since = [&](std::chrono::steady_clock::time_point t) {
@@ -895,6 +896,7 @@ int isomp_multi(qf_ctx **ctxs, int k, double dt, int steps, double tol, int mini
     bool together = true;
     for (int r = 0; r < k; ++r) {
         QF_TRY(check_ctx(ctxs[r]));
+        QF_TRY(qf_refuse_forcing(ctxs[r], name));
         if (is_c64<S> && !ctxs[r]->c64) {
             qf_set_error("%s: context %d holds no complex64 state (qf_c64_upload_W)", name, r);
             return QF_ERR_STATE;

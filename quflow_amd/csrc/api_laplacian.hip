@@ -219,6 +219,66 @@ int qf_hamiltonian_energy(qf_ctx *ctx, double *H)
     return QF_OK;
 }
 
+// ---- the installed forcing of the flow (include/quflow_hip.h; applied by qf_launch_forcing_affine, hooks.hip)
+int qf_set_forcing(qf_ctx *ctx, const void *F0_host, unsigned long long F0_key, double a_W, double a_P, double a_lap)
+{
+    QF_TRY(check_ctx(ctx));
+    if (!QF_FINITE(a_W) || !QF_FINITE(a_P) || !QF_FINITE(a_lap)) {
+        qf_set_error("qf_set_forcing: the coefficients must be finite (a_W=%g, a_P=%g, a_lap=%g)", a_W, a_P, a_lap);
+        return QF_ERR_INVALID;
+    }
+    const size_t NN = (size_t)ctx->N * ctx->N;
+    ctx->forcing_on = false;       // nothing is in force until the pattern is in place
+    if (F0_host) {
+        const unsigned long long fp = sample_fingerprint(static_cast<const double *>(F0_host), 2 * NN);
+        if (!(ctx->forcing_f0 && F0_key != 0 && ctx->forcing_key == F0_key && ctx->forcing_fp == fp)) {
+            if (!ctx->forcing_f0) QF_HIP(hipMalloc((void **)&ctx->forcing_f0, NN * sizeof(cplx)));
+            ctx->forcing_key = 0;
+            // (pageable source: hipMemcpyAsync returns after staging, the caller's matrix is free on return)
+            QF_HIP(hipMemcpyAsync(ctx->forcing_f0, F0_host, NN * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+            ctx->forcing_key = F0_key;
+            ctx->forcing_fp = fp;
+        }
+    }
+    ctx->forcing_f0_on = F0_host != nullptr;
+    ctx->forcing_aW = a_W;
+    ctx->forcing_aP = a_P;
+    ctx->forcing_alap = a_lap;
+    ctx->forcing_on = true;
+    return QF_OK;
+}
+
+int qf_clear_forcing(qf_ctx *ctx)
+{
+    QF_TRY(check_ctx(ctx));
+    ctx->forcing_on = false;
+    ctx->forcing_f0_on = false;
+    return QF_OK;
+}
+
+int qf_forcing(qf_ctx *ctx, const void *P_host, const void *W_host, void *F_host)
+{
+    QF_TRY(check_ctx(ctx));
+    const bool on_device = !P_host && !W_host && !F_host;
+    if (!on_device && (!P_host || !W_host || !F_host)) {
+        qf_set_error("qf_forcing: null buffer");
+        return QF_ERR_INVALID;
+    }
+    if (!ctx->forcing_on) {
+        qf_set_error("qf_forcing: no forcing is installed (qf_set_forcing)");
+        return QF_ERR_STATE;
+    }
+    if (on_device)      // the kernel alone, queued on the stream: resident state, the stream-matrix buffer as it stands
+        return qf_launch_forcing_affine(ctx, ctx->Phalf, ctx->W, ctx->PW, 1.0, 1.0);
+    const size_t bytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    QF_HIP(hipMemcpyAsync(ctx->Phalf, P_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    QF_HIP(hipMemcpyAsync(ctx->stage, W_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    QF_TRY(qf_launch_forcing_affine(ctx, ctx->Phalf, ctx->stage, ctx->PW, 1.0, 1.0));
+    QF_HIP(hipMemcpyAsync(F_host, ctx->PW, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
 int qf_factor_cache_stats(qf_ctx *ctx, int *entries, unsigned long long *device_bytes)
 {
     QF_TRY(check_ctx(ctx));

@@ -25,6 +25,7 @@ int qf_erk(qf_ctx *ctx, int method, double dt, int steps, int skewh)
         qf_set_error("qf_erk: steps must be >= 0");
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, "qf_erk"));
     const double inv_hb = 1.0 / qf_hbar(ctx->N);
     ctx->w_skew_known = false;
     bool one_product = false;
@@ -92,6 +93,7 @@ int qf_erk_states(qf_ctx *ctx, void *states_host, int k, int method, double dt, 
         qf_set_error("qf_erk_states: bad arguments (method %d, steps %d, k %d)", method, steps, k);
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, "qf_erk_states"));
     const int N = ctx->N;
     const size_t mbytes = (size_t)N * N * sizeof(cplx);
     const double inv_hb = 1.0 / qf_hbar(N);
@@ -309,6 +311,7 @@ static int isomp_simple_impl(qf_ctx *ctx, double dt, int steps, const qf_isomp_h
         qf_set_error("qf_isomp_simple: steps must be >= 0");
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, hooks ? "qf_isomp_simple_hooked" : "qf_isomp_simple"));
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     const double stepsize = dt / qf_hbar(ctx->N);           // isospectral.py:281
     ctx->w_skew_known = false;
@@ -381,6 +384,7 @@ static int isomp_quasinewton_impl(qf_ctx *ctx, double dt, int steps, double tol,
         qf_set_error("qf_isomp_quasinewton: steps must be >= 0 and maxit >= 1");
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, hooks ? "qf_isomp_quasinewton_hooked" : "qf_isomp_quasinewton"));
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     const double stepsize = dt / qf_hbar(ctx->N);           // isospectral.py:187
     ctx->w_skew_known = false;
@@ -675,6 +679,7 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         qf_set_error("qf_isomp_states: bad arguments (k=%d, steps=%d, magnetic=%d)", k, steps, magnetic);
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, "qf_isomp_states"));
     ctx->stack_k = 0;        // (host in / host out: the stack's buffers are this call's scratch)
     QF_TRY(stack_upload(ctx, states_host, k));
     return states_body(ctx, states_host, k, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats_out, nullptr);
@@ -729,6 +734,7 @@ int qf_states_advance_diag(qf_ctx *ctx, double dt, int steps, double tol, int mi
         qf_set_error("qf_states_advance: bad arguments (resident k=%d, steps=%d, magnetic=%d)", ctx->stack_k, steps, magnetic);
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, "qf_states_advance"));
     return states_body(ctx, nullptr, ctx->stack_k, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats_out, mhd_out);
 }
 

@@ -10,6 +10,9 @@
 //     forcing             : P and Whalf down (Whalf only once if the Hamiltonian took it), F up
 //     strang_splitting    : W down and up, twice per step          (or a resident tridiagonal solve: none)
 //     callback            : W and the commutator down, once per step
+// An AFFINE forcing installed on the context (qf_set_forcing) is no hook: k_forcing_affine forms it from Phalf and Whalf where
+// the loop would call the hook, and nothing crosses PCIe for it; qf_isomp_forced is the same loop on the context's resident
+// state (no transfer at all).
 // The two products run on the fp64 matrix cores (k_zgemm, plain stores), one pass (k_hook_assemble)
 // forms the commutator, dW, Whalf and the residual row sums, one pass (k_hook_update) the step's
 // update; the exit test reads one scalar back per iteration (the hooks synchronise the host anyway).
@@ -197,6 +200,55 @@ __global__ __launch_bounds__(256) void k_erk_stage_forced(size_t n, const cplx *
     }
 }
 
+// The installed affine forcing (qf_set_forcing), one pass, one entry per lane (16-byte loads and stores, consecutive lanes
+// on consecutive entries):
+//     p = Ph * pscale;  f = F0;  f += a_W X;  f += a_P p;  f += a_lap (Delta X);  out = s f
+// on real and imaginary parts separately, every product and sum rounded on its own (no fused multiply-add), a term whose
+// coefficient is zero (or an absent F0) skipped altogether: which terms there are is the template argument TERMS (bit 0 F0,
+// 1 a_W, 2 a_P, 3 a_lap), decided by the launcher.  Delta X is qf_laplace_entry: k_laplace's bits.  N <= 8192: the flat
+// index (and one grid stride past its end) fits 32 bits.
+template <int TERMS>
+__global__ __launch_bounds__(256) void k_forcing_affine(int N, unsigned n, const cplx *__restrict__ F0, const cplx *__restrict__ X,
+                                                         const cplx *__restrict__ Ph, cplx *__restrict__ out, double aW, double aP,
+                                                         double alap, double pscale, double s)
+{
+    for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < n; e += gridDim.x * 256u) {
+        double fr = 0.0, fi = 0.0;
+        if (TERMS & 1) {
+            const cplx f = F0[e];
+            fr = f.x;
+            fi = f.y;
+        }
+        if (TERMS & 2) {
+            const cplx x = X[e];
+            fr = fr + aW * x.x;
+            fi = fi + aW * x.y;
+        }
+        if (TERMS & 4) {
+            const cplx p = Ph[e];
+            const double pr = p.x * pscale, pi = p.y * pscale;
+            fr = fr + aP * pr;
+            fi = fi + aP * pi;
+        }
+        if (TERMS & 8) {
+            const int i = (int)(e / (unsigned)N), j = (int)(e - (unsigned)i * (unsigned)N);
+            const cplx l = qf_laplace_entry<double, cplx>(N, X, i, j);
+            fr = fr + alap * l.x;
+            fi = fi + alap * l.y;
+        }
+        out[e] = make_double2(s * fr, s * fi);
+    }
+}
+
+template <int TERMS>
+void launch_forcing_terms(qf_ctx *ctx, const cplx *Ph, const cplx *X, cplx *out, double pscale, double s)
+{
+    const unsigned n = (unsigned)ctx->N * (unsigned)ctx->N;
+    const unsigned blocks = (n + 255u) / 256u < 2048u ? (n + 255u) / 256u : 2048u;      // (8 per CU; the rest by the grid stride)
+    hipLaunchKernelGGL(k_forcing_affine<TERMS>, dim3(blocks), dim3(256), 0, ctx->stream, ctx->N, n, ctx->forcing_f0, X, Ph,
+                       out, ctx->forcing_aW, ctx->forcing_aP, ctx->forcing_alap, pscale, s);
+}
+
 int launch_assemble(qf_ctx *ctx, bool skew, cplx *PW, cplx *dW, const cplx *F, const cplx *W, cplx *Whalf, const cplx *dW_old,
                     double *rowpart)
 {
@@ -263,10 +315,32 @@ int read_scalar_sync(qf_ctx *ctx, const double *dev, double *out)
 
 }  // namespace
 
-extern "C" {
+int qf_launch_forcing_affine(qf_ctx *ctx, const cplx *Ph, const cplx *X, cplx *out, double pscale, double s)
+{
+    if (!ctx->forcing_on) {
+        qf_set_error("qf_launch_forcing_affine: no forcing is installed");
+        return QF_ERR_STATE;
+    }
+    typedef void (*launcher)(qf_ctx *, const cplx *, const cplx *, cplx *, double, double);
+    static const launcher table[16] = {
+        launch_forcing_terms<0>,  launch_forcing_terms<1>,  launch_forcing_terms<2>,  launch_forcing_terms<3>,
+        launch_forcing_terms<4>,  launch_forcing_terms<5>,  launch_forcing_terms<6>,  launch_forcing_terms<7>,
+        launch_forcing_terms<8>,  launch_forcing_terms<9>,  launch_forcing_terms<10>, launch_forcing_terms<11>,
+        launch_forcing_terms<12>, launch_forcing_terms<13>, launch_forcing_terms<14>, launch_forcing_terms<15>};
+    const int terms = (ctx->forcing_f0_on ? 1 : 0) | (ctx->forcing_aW != 0.0 ? 2 : 0) | (ctx->forcing_aP != 0.0 ? 4 : 0) |
+                      (ctx->forcing_alap != 0.0 ? 8 : 0);
+    table[terms](ctx, Ph, X, out, pscale, s);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
 
-int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
-                    int compsum, int reinitialize, const qf_isomp_hooks *hooks, qf_isomp_stats *stats_out)
+namespace {
+
+// The loop of qf_isomp_hooked and of qf_isomp_forced, written once.  states_host != nullptr: the (k,N,N) state comes from
+// the host and goes back there;  nullptr (k == 1): it is taken from the context's resident state ctx->W and returned to it
+// by device copies -- no N^2 transfer in either direction, no pinned staging.
+int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
+                int compsum, int reinitialize, const qf_isomp_hooks *hooks, qf_isomp_stats *stats_out)
 {
     if (!ctx) {
         qf_set_error("null qf_ctx");
@@ -281,11 +355,19 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         qf_set_error("maxit must be at minit.");
         return QF_ERR_INVALID;
     }
-    if (!states_host || !hooks || k < 1 || steps < 0) {
+    const bool resident = states_host == nullptr;
+    if (!hooks || k < 1 || steps < 0 || (resident && k != 1)) {
         qf_set_error("qf_isomp_hooked: bad arguments (k=%d, steps=%d)", k, steps);
         return QF_ERR_INVALID;
     }
-    if (compsum && hooks->forcing && steps > 0) {   // isospectral.py:588-589
+    // an installed forcing (qf_set_forcing) is applied on the device where the host hook is absent: one (N,N) state, not magmp
+    if (ctx->forcing_on && (k > 1 || hooks->magnetic)) return qf_refuse_forcing(ctx, k > 1 ? "qf_isomp_hooked on a stack" : "qf_isomp_hooked (magmp)");
+    if (ctx->forcing_on && hooks->forcing) {
+        qf_set_error("qf_isomp_hooked: a forcing is installed on this context (qf_set_forcing) and a `forcing` hook is given as well");
+        return QF_ERR_UNSUPPORTED;
+    }
+    const bool dev_forced = ctx->forcing_on;
+    if (compsum && (hooks->forcing || dev_forced) && steps > 0) {   // isospectral.py:588-589
         qf_set_error("Compensated sum with forcing is not yet implemented.");
         return QF_ERR_UNSUPPORTED;
     }
@@ -299,7 +381,7 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         return QF_ERR_INVALID;
     }
     const bool skew = hooks->skewh != 0;
-    const bool forced = hooks->forcing != nullptr;
+    const bool forced = hooks->forcing != nullptr || dev_forced;
     const bool foreign = hooks->hamiltonian != nullptr;
     ctx->w_skew_known = false;
     ctx->increment_valid = false;
@@ -317,13 +399,14 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
     }
     const size_t per = 7;
     QF_TRY(need_device(ctx, per * k + 4 + ((per_state || (states_p_open && k <= 48)) ? (size_t)k : 0)));
-    QF_TRY(need_host(ctx, k));
+    if (!resident) QF_TRY(need_host(ctx, k));
     struct st { cplx *W, *dW[2], *Whalf, *PW, *F, *kc; int cur; };
     std::vector<st> S((size_t)k);
     for (int j = 0; j < k; ++j) {
         cplx **b = &ctx->multi[per * j];
         S[j] = {b[0], {b[1], b[2]}, b[3], b[4], b[5], b[6], 0};
-        QF_HIP(hipMemcpyAsync(S[j].W, (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
+        if (resident) QF_HIP(hipMemcpyAsync(S[j].W, ctx->W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+        else QF_HIP(hipMemcpyAsync(S[j].W, (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
         QF_HIP(hipMemsetAsync(S[j].dW[0], 0, mbytes, ctx->stream));                      // dW = zeros_like(W), :430
         QF_HIP(hipMemcpyAsync(S[j].Whalf, S[j].W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
         if (compsum) QF_HIP(hipMemsetAsync(S[j].kc, 0, mbytes, ctx->stream));             // :457
@@ -434,7 +517,11 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
                 QF_TRY(qf_launch_zgemm(ctx, BT, ctx->Phalf, BTP, nullptr));         // BThetaPhalf = BThetacomm @ Phalf
             }
             // ---- forcing(Phalf / vareps, Whalf[, time + dt/2]) * dt/2     :512-520  (before Whalf is rewritten)
-            if (forced) {
+            if (dev_forced) {
+                // the installed forcing, straight into the loop's F: p = Phalf * (1/vareps), F = (dt/2) f -- the roundings of the
+                // host route below
+                QF_TRY(qf_launch_forcing_affine(ctx, ctx->Phalf, S[0].Whalf, S[0].F, 1.0 / vareps, dt / 2));
+            } else if (forced) {
                 if (!foreign) QF_HIP(hipMemcpyAsync(hP, ctx->Phalf, mbytes, hipMemcpyDeviceToHost, ctx->stream));
                 if (!have_whalf_host) QF_TRY(download_stack(hW, 1));
                 else QF_HIP(hipStreamSynchronize(ctx->stream));
@@ -552,7 +639,8 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         if (hooks->has_time) time += dt;                            // :598-599
         QF_TRY(strang_half());
     }
-    for (int j = 0; j < k; ++j)
+    if (resident) QF_HIP(hipMemcpyAsync(ctx->W, S[0].W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    for (int j = 0; j < k && !resident; ++j)
         QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].W, mbytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     if (stats_out) {
@@ -562,6 +650,33 @@ int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
         stats_out->last_resnorm = resnorm;
     }
     return QF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qf_isomp_hooked(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
+                    int compsum, int reinitialize, const qf_isomp_hooks *hooks, qf_isomp_stats *stats_out)
+{
+    if (ctx && !states_host) {
+        qf_set_error("qf_isomp_hooked: bad arguments (k=%d, steps=%d)", k, steps);
+        return QF_ERR_INVALID;
+    }
+    return hooked_body(ctx, states_host, k, dt, steps, tol, minit, maxit, compsum, reinitialize, hooks, stats_out);
+}
+
+// The hooked loop on the context's RESIDENT state with the installed forcing (none: no force term) and Hamiltonian: k = 1,
+// the skew-Hermitian branch, no host hook; the Strang half step is the resident tridiagonal solve.
+int qf_isomp_forced(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize,
+                    const double *strang_table, unsigned long long strang_key, qf_isomp_stats *stats_out)
+{
+    qf_isomp_hooks hooks = {};
+    hooks.skewh = 1;
+    hooks.solve_skewh = 1;
+    hooks.strang_table = strang_table;
+    hooks.strang_key = strang_key;
+    return hooked_body(ctx, nullptr, 1, dt, steps, tol, minit, maxit, 0, reinitialize, &hooks, stats_out);
 }
 
 // euler / heun / rk4 (quflow/integrators/erk.py:19-160) with `forcing(P, W)` and / or a foreign
@@ -578,6 +693,11 @@ int qf_erk_hooked(qf_ctx *ctx, void *W_host, int method, double dt, int steps, c
         qf_set_error("qf_erk_hooked: bad arguments (method=%d, steps=%d)", method, steps);
         return QF_ERR_INVALID;
     }
+    if (ctx->forcing_on && hooks->forcing) {
+        qf_set_error("qf_erk_hooked: a forcing is installed on this context (qf_set_forcing) and a `forcing` hook is given as well");
+        return QF_ERR_UNSUPPORTED;
+    }
+    const bool dev_forced = ctx->forcing_on;       // the installed forcing: formed on the device, unscaled as the hook's is
     const int N = ctx->N;
     const size_t NN = (size_t)N * N, mbytes = NN * sizeof(cplx);
     const double inv_hb = 1.0 / qf_hbar(N);
@@ -603,7 +723,9 @@ int qf_erk_hooked(qf_ctx *ctx, void *W_host, int method, double dt, int steps, c
         }
         QF_TRY(qf_launch_zgemm(ctx, P, X, A, nullptr));      // bracket(P, X) = (P@X - X@P)/hbar, geometry.py:41-49
         QF_TRY(qf_launch_zgemm(ctx, X, P, B, nullptr));
-        if (hooks->forcing) {
+        if (dev_forced) {
+            QF_TRY(qf_launch_forcing_affine(ctx, P, X, F, 1.0, 1.0));
+        } else if (hooks->forcing) {
             if (!hooks->hamiltonian) QF_HIP(hipMemcpyAsync(hP, P, mbytes, hipMemcpyDeviceToHost, ctx->stream));
             if (!have_x) QF_HIP(hipMemcpyAsync(hX, X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
             QF_HIP(hipStreamSynchronize(ctx->stream));
@@ -613,7 +735,7 @@ int qf_erk_hooked(qf_ctx *ctx, void *W_host, int method, double dt, int steps, c
         }
         return QF_OK;
     };
-    const cplx *Fk = hooks->forcing ? F : nullptr;
+    const cplx *Fk = (hooks->forcing || dev_forced) ? F : nullptr;
     auto stage = [&](cplx *acc_, double c_acc, cplx *Wp_, double c_wp, cplx *Wout_, double c_fin) -> int {
         hipLaunchKernelGGL(k_erk_stage_forced, dim3(blocks), dim3(256), 0, ctx->stream, NN, A, B, Fk, inv_hb, W, acc_, c_acc, Wp_,
                            c_wp, Wout_, c_fin);
@@ -660,6 +782,7 @@ int qf_erk_states_hooked(qf_ctx *ctx, void *states_host, int k, int method, doub
         qf_set_error("qf_erk_states_hooked: bad arguments (k=%d, method=%d, steps=%d)", k, method, steps);
         return QF_ERR_INVALID;
     }
+    QF_TRY(qf_refuse_forcing(ctx, "qf_erk_states_hooked"));
     const int N = ctx->N;
     const size_t NN = (size_t)N * N, mbytes = NN * sizeof(cplx);
     const double inv_hb = 1.0 / qf_hbar(N);

@@ -422,6 +422,13 @@ struct qf_ctx {
     cplx *ham_offset = nullptr;
     unsigned long long ham_offset_key = 0, ham_offset_fp = 0;
     bool ham_table = false, ham_offset_on = false;
+    // the installed forcing F(P, W) = F0 + a_W W + a_P P + a_lap Delta W (qf_set_forcing): the pattern F0 in a buffer of the
+    // context's own, allocated on first use and kept (with the key and fingerprint of what it holds) when the forcing is
+    // cleared; forcing_on says whether one is in force, forcing_f0_on whether it has a pattern.
+    cplx *forcing_f0 = nullptr;
+    unsigned long long forcing_key = 0, forcing_fp = 0;
+    bool forcing_on = false, forcing_f0_on = false;
+    double forcing_aW = 0.0, forcing_aP = 0.0, forcing_alap = 0.0;
 
     // spherical-harmonics transforms (quantization.hip): basis resident in HBM, m-major staging
     double *basis = nullptr;     // N(N+1)(2N+1)/6 doubles (quantization.py:68-113), uploaded once
@@ -514,6 +521,21 @@ inline void qf_plan_note(qf_ctx *ctx, unsigned long long key, const char *fmt, .
     va_end(ap);
     s.key = key;
 }
+
+// An entry point that cannot apply an installed forcing says so instead of dropping the force (include/quflow_hip.h)
+inline int qf_refuse_forcing(const qf_ctx *ctx, const char *who)
+{
+    if (ctx && ctx->forcing_on) {
+        qf_set_error("%s: a forcing is installed on this context (qf_set_forcing) and this entry point cannot apply it; "
+                     "qf_isomp_forced, qf_isomp_hooked (k = 1) and qf_erk_hooked follow an installed forcing", who);
+        return QF_ERR_UNSUPPORTED;
+    }
+    return QF_OK;
+}
+
+// ---- hooks.hip
+// out = s * (F0 + a_W X + a_P (pscale Ph) + a_lap Delta X) of the installed forcing, in the order include/quflow_hip.h fixes
+int qf_launch_forcing_affine(qf_ctx *ctx, const cplx *Ph, const cplx *X, cplx *out, double pscale, double s);
 
 // ---- poisson.hip
 int qf_launch_lap_table(qf_ctx *ctx, int bc, double *lap_dev);

@@ -124,6 +124,30 @@ def _hamiltonian_on(ctx, ham):
         ham.uninstall(ctx)
 
 
+def _installable_forcing(f, W):
+    """`f` if it is an AffineForcing that this call installs on its device context -- skew-Hermitian mode, one (N,N)
+    complex128 state -- else None (the instance is then the host callable `forcing(P, W)` it also is)."""
+    if (_laplacian.forcing_installable(f) and _SKEW_HERM_ and isinstance(W, np.ndarray) and W.ndim == 2
+            and W.shape[0] == W.shape[1] and W.dtype == np.complex128):
+        f.check_size(W.shape[-1])
+        return f
+    return None
+
+
+@contextlib.contextmanager
+def _forcing_on(ctx, aff):
+    """The call's AffineForcing installed on its context for the call alone (the twin of _hamiltonian_on): a later call on
+    the cached context must find no forcing again -- also after an error."""
+    if aff is None:
+        yield
+        return
+    aff.install(ctx)
+    try:
+        yield
+    finally:
+        aff.uninstall(ctx)
+
+
 def isomp_fixedpoint(W,
                      dt,
                      steps=100,
@@ -158,6 +182,9 @@ def isomp_fixedpoint(W,
         general commutator of select_skewherm(False) (:504-505), and hooks / compsum on (k,N,N) stacks:
         qf_isomp_hooked -- W, dW, Whalf, the products and the Kahan term never leave the device; per
         iteration only what the hook reads goes down and what it returns comes up.
+      * `forcing=AffineForcing(...)` on an (N,N) complex128 state in skew-Hermitian mode is no host hook: it is installed
+        on the device context for the call and one kernel forms the force term inside that loop (nothing crosses PCIe
+        for it); a TridiagonalHamiltonian and a ViscDampStep are followed on the device next to it.
     """
     # Check input (AssertionError like isospectral.py:400-401)
     assert minit >= 1, "minit must be at least 1."
@@ -490,7 +517,8 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
     k = 1 if squeeze else W.shape[0]
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     table = _HookTable(N, k, squeeze)
-    if forcing is not None:
+    aff = _installable_forcing(forcing, W)        # installed on the device for this call: no forcing hook
+    if forcing is not None and aff is None:
         table.set_forcing(forcing, _takes_time(forcing, (Wc, Wc), time))
     if not native:
         # one stream matrix for all states or one per state?  Not asked here: the stepper's first evaluation tells
@@ -510,7 +538,7 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
     ctx = get_stepper_context(N, device)
     st = _lib.IsompStats()
     tol_c, tol_report = _device_tol(W, dt, tol, compsum)
-    with _hamiltonian_on(ctx, ham):       # (`native`: the device's own solve, of what is installed)
+    with _hamiltonian_on(ctx, ham), _forcing_on(ctx, aff):       # (`native`: the device's own solve, of what is installed)
         rc = ctx._lib.qf_isomp_hooked(ctx.handle, ptr(Wc), k, float(dt), int(steps), tol_c, int(minit),
                                       int(maxit), int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(table.c),
                                       ctypes.byref(st))
@@ -792,12 +820,14 @@ def _erk_hooked(method, W, dt, steps, hamiltonian, forcing, device):
     N = W.shape[-1]
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     table = _HookTable(N, 1, True)
-    if forcing is not None:
+    aff = _installable_forcing(forcing, W)        # installed on the device for this call: no forcing hook
+    if forcing is not None and aff is None:
         table.set_forcing(forcing, False)
     if not _is_native_hamiltonian(hamiltonian):
         table.set_hamiltonian(hamiltonian, False)
     ctx = get_stepper_context(N, device)
-    rc = ctx._lib.qf_erk_hooked(ctx.handle, ptr(Wc), _lib.ERK_METHODS[method], float(dt), int(steps), ctypes.byref(table.c))
+    with _forcing_on(ctx, aff):
+        rc = ctx._lib.qf_erk_hooked(ctx.handle, ptr(Wc), _lib.ERK_METHODS[method], float(dt), int(steps), ctypes.byref(table.c))
     table.check(rc)
     if Wc is not W:
         W[...] = Wc
@@ -904,9 +934,17 @@ class DeviceTrajectory:
     semantics of one `integrator(W, dt, steps=...)` call of simulation.solve
     (quflow/simulation.py:782-798): dW restarts from zero (isospectral.py:430)."""
 
-    def __init__(self, W0, device=None, hamiltonian=None):
+    forcing = None              # (class defaults: from_shr / from_fun build instances without __init__)
+    strang_splitting = None
+    hamiltonian = None
+
+    def __init__(self, W0, device=None, hamiltonian=None, forcing=None, strang_splitting=None):
         """`hamiltonian`: None / solve_poisson for the built-in one, or a TridiagonalHamiltonian, which is installed on the
-        trajectory's private context for its whole life: advance, advance_erk and advance_lu follow it."""
+        trajectory's private context for its whole life: advance, advance_erk and advance_lu follow it.
+        `forcing`: None or an AffineForcing, installed for the trajectory's life (set_forcing replaces it between advances);
+        `strang_splitting`: None or a ViscDampStep, the viscous / damped half step around every step.  With either one
+        `advance` is the hooked loop on the resident state (qf_isomp_forced: the bits of
+        isomp(W, dt, steps, forcing=..., strang_splitting=...), nothing crosses PCIe); complex128 only."""
         # a complex64 initial state makes a single-precision trajectory (float32 solve, complex64 products:
         # what the reference does with complex64 input); anything else is complex128
         self.c64 = np.asarray(W0).dtype == np.complex64 and _laplacian.single_precision_on_device()
@@ -922,6 +960,17 @@ class DeviceTrajectory:
         elif not _is_native_hamiltonian(hamiltonian):
             raise TypeError("DeviceTrajectory takes the built-in Hamiltonian or a TridiagonalHamiltonian; any other callable "
                             "runs through isomp(..., hamiltonian=...)")
+        if forcing is not None and not isinstance(forcing, _laplacian.AffineForcing):
+            raise TypeError("DeviceTrajectory takes an AffineForcing; any other callable runs through isomp(..., forcing=...)")
+        if strang_splitting is not None and not isinstance(strang_splitting, _laplacian.ViscDampStep):
+            raise TypeError("DeviceTrajectory takes a ViscDampStep; any other callable runs through "
+                            "isomp(..., strang_splitting=...)")
+        if forcing is not None or strang_splitting is not None:
+            if self.c64 or not (_SKEW_HERM_ and _laplacian._SKEW_HERM_):
+                raise NotImplementedError("a resident forcing / strang_splitting needs complex128 data and the "
+                                          "skew-Hermitian mode (select_skewherm(True))")
+            if forcing is not None:
+                forcing.check_size(self.N)
         # a private context: the trajectory owns its device state (the shared per-N context of
         # get_context() is scratch for the host-in/host-out entry points)
         self.ctx = Context(self.N, default_device() if device is None else device)
@@ -934,7 +983,28 @@ class DeviceTrajectory:
                 self.ctx.close()
                 raise
             self.hamiltonian = hamiltonian
+        self.strang_splitting = strang_splitting
+        try:
+            self.set_forcing(forcing)
+        except Exception:
+            self.ctx.close()
+            raise
         _lib.check((self._lib.qf_c64_upload_W if self.c64 else self._lib.qf_upload_W)(self.ctx.handle, ptr(W0)))
+
+    def set_forcing(self, forcing):
+        """Replace the installed forcing between advances (None: none): a run that redraws its pattern F0 per chunk."""
+        if forcing is None:
+            if self.forcing is not None:
+                _laplacian.AffineForcing.uninstall(self.ctx)
+            self.forcing = None
+            return
+        if not isinstance(forcing, _laplacian.AffineForcing):
+            raise TypeError("DeviceTrajectory takes an AffineForcing; any other callable runs through isomp(..., forcing=...)")
+        if self.c64 or not (_SKEW_HERM_ and _laplacian._SKEW_HERM_):
+            raise NotImplementedError("a resident forcing needs complex128 data and the skew-Hermitian mode "
+                                      "(select_skewherm(True))")
+        forcing.install(self.ctx)
+        self.forcing = forcing
 
     def hamiltonian_energy(self):
         """H = -inner_L2(P, W - F)/2 of the resident state with P = T^-1 (W - F) of the installed Hamiltonian (the built-in
@@ -956,7 +1026,24 @@ class DeviceTrajectory:
         args = (self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit), int(bool(compsum)),
                 int(bool(reinitialize)), ctypes.byref(st))
         out = {}
-        if self.c64:
+        if self.forcing is not None or self.strang_splitting is not None:
+            # the hooked loop on the resident state, with what is installed (qf_isomp_forced)
+            if compsum and self.forcing is not None:
+                raise NotImplementedError("Compensated sum with forcing is not yet implemented.")     # isospectral.py:588-589
+            if compsum:
+                raise NotImplementedError("compsum with a resident strang_splitting: run it through "
+                                          "isomp(..., strang_splitting=..., compsum=True)")
+            tab, key = (None, 0)
+            if self.strang_splitting is not None:
+                tab, key = self.strang_splitting.table_and_key(self.N, dt / 2)
+                tab = np.ascontiguousarray(tab, dtype=np.float64)
+            _lib.check(self._lib.qf_isomp_forced(self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit),
+                                                 int(bool(reinitialize)), None if tab is None else ptr(tab),
+                                                 ctypes.c_ulonglong(key), ctypes.byref(st)))
+            if diagnostics:
+                e, s = self.diagnostics()
+                out = {"energy": e, "enstrophy": s}
+        elif self.c64:
             _lib.check(self._lib.qf_c64_isomp(*args))
             if diagnostics:
                 e, s = self.diagnostics()
@@ -977,6 +1064,7 @@ class DeviceTrajectory:
     def advance_erk(self, method, dt, steps):
         """`steps` steps of euler / heun / rk4 (quflow/integrators/erk.py) on the resident state."""
         self._double_only("advance_erk")
+        self._unforced_only("advance_erk")
         _lib.check(self._lib.qf_erk(self.ctx.handle, _lib.ERK_METHODS[method], float(dt), int(steps),
                                     int(_laplacian._SKEW_HERM_)))
         evals = {"euler": 1, "heun": 2, "rk4": 4}[method]
@@ -986,6 +1074,7 @@ class DeviceTrajectory:
     def advance_lu(self, method, dt, steps, tol=-1.0, maxit=10):
         """`steps` steps of isomp_simple / isomp_quasinewton (isospectral.py:155-335) on the resident state."""
         self._double_only("advance_lu")
+        self._unforced_only("advance_lu")
         st = _lib.IsompStats()
         if method == "isomp_simple":
             _lib.check(self._lib.qf_isomp_simple(self.ctx.handle, float(dt), int(steps)))
@@ -1001,6 +1090,11 @@ class DeviceTrajectory:
             raise NotImplementedError("%s on a complex64 trajectory: the resident single-precision state has the "
                                       "stepper (advance), diagnostics, upload and download; convert to complex128 "
                                       "for the rest" % what)
+
+    def _unforced_only(self, what):
+        if self.forcing is not None:
+            raise NotImplementedError("%s with an installed forcing: the resident forced run has the isomp stepper "
+                                      "(advance); euler / heun / rk4 take forcing= on host arrays" % what)
 
     def diagnostics(self):
         """(energy_euler, enstrophy) of the resident state, quflow/physics.py:26-38."""

@@ -428,3 +428,106 @@ def installable(h):
     """`h` is a TridiagonalHamiltonian and the process is in the mode in which the device follows an installed one: the
     skew-Hermitian solve (select_skewherm(True), the default)."""
     return isinstance(h, TridiagonalHamiltonian) and _SKEW_HERM_
+
+
+class AffineForcing:
+    """`forcing=` of the steppers for the forcing that is affine in the state,
+
+        F(P, W) = F0 + a_W W + a_P P + a_lap Delta W          (a_* real, F0 a fixed skew-Hermitian pattern)
+
+    -- a fixed pattern, Rayleigh friction (a_W < 0), a large-scale drag on the stream function (a_P) and viscosity
+    (a_lap > 0) -- as an object the device follows: isomp / isomp_fixedpoint and euler / heun / rk4 on an (N,N) complex128
+    state in skew-Hermitian mode, DeviceTrajectory and quflow_amd.solve install it on the device context they run on
+    (qf_set_forcing), where one kernel forms the force term from the matrices the loop already holds; nothing crosses
+    PCIe for it.  Elsewhere -- stacks, magmp, select_skewherm(False), complex64 data -- an instance is the callable
+    `forcing(P, W)` it also is and takes the host-hook route of any callable.
+
+    The order of operations is fixed.  Where a loop evaluates the forcing at a matrix X (Whalf in the isomp loop, the stage
+    argument in euler / heun / rk4) with the stream matrix Ph as the loop holds it, a stream-matrix scale pscale and an
+    output scale s, the device computes per entry, on real and imaginary parts separately, every product and sum rounded on
+    its own (no fused multiply-add):
+
+        p = Ph * pscale
+        f = F0[e]                        (0 when there is no F0)
+        f = f + a_W * X[e]               (term skipped entirely when a_W == 0.0)
+        f = f + a_P * p                  (skipped when a_P == 0.0)
+        f = f + a_lap * (Delta X)[e]     (skipped when a_lap == 0.0; Delta X as quflow_amd.laplace gives it)
+        out = s * f
+
+    isomp loop: pscale = 1 / (dt / (2 hbar)), s = dt / 2 (what the host-hook route does to P before and to F behind the
+    call: isospectral.py:512-520); explicit loops and `__call__`: pscale = s = 1.  A numpy callable that repeats these lines
+    on `.real` / `.imag` float64 arrays, with Delta X from quflow_amd.laplace, gives the same numbers bit for bit.
+
+    F0 must be finite and EXACTLY skew-Hermitian (F0 == -F0^H entry by entry), the coefficients finite real numbers:
+    ValueError / TypeError otherwise.  Instances are immutable; a run that redraws its pattern makes a new one per chunk
+    (DeviceTrajectory.set_forcing)."""
+
+    def __init__(self, F0=None, a_W=0.0, a_P=0.0, a_lap=0.0):
+        coeff = []
+        for name, a in (("a_W", a_W), ("a_P", a_P), ("a_lap", a_lap)):
+            if isinstance(a, (complex, np.complexfloating)) or isinstance(a, (str, bytes, bool)) or not np.isscalar(a):
+                raise TypeError("%s must be a real number, got %r" % (name, a))
+            a = float(a)
+            if not np.isfinite(a):
+                raise ValueError("%s must be finite, got %r" % (name, a))
+            coeff.append(a)
+        self.a_W, self.a_P, self.a_lap = coeff
+        self.F0 = None
+        self.N = None
+        self.F0_key = 0
+        if F0 is not None:
+            F0 = np.array(F0, dtype=np.complex128, order="C")
+            if F0.ndim != 2 or F0.shape[0] != F0.shape[1] or F0.shape[0] < 2:
+                raise ValueError("F0 must be an (N,N) matrix, got shape %s" % (F0.shape,))
+            if not np.all(np.isfinite(F0.view(np.float64))):
+                raise ValueError("F0 must be finite")
+            if not np.array_equal(F0, -F0.conj().T):
+                raise ValueError("F0 must be exactly skew-Hermitian (F0 == -F0^H entry by entry): project it with "
+                                 "F0 = (F0 - F0^H) / 2 first")
+            F0.setflags(write=False)
+            self.F0 = F0
+            self.N = int(F0.shape[0])
+            self.F0_key = _sample_key("forcing_f0", F0)
+
+    def check_size(self, N):
+        if self.N is not None and int(N) != self.N:
+            raise ValueError("the forcing was built for N=%d, the state has N=%d" % (self.N, int(N)))
+
+    # ---- installing on a device context (the steppers and the device objects call these)
+    def install(self, ctx):
+        self.check_size(ctx.N)
+        _lib.check(ctx._lib.qf_set_forcing(ctx.handle, None if self.F0 is None else ptr(self.F0),
+                                           ctypes.c_ulonglong(self.F0_key), self.a_W, self.a_P, self.a_lap))
+
+    @staticmethod
+    def uninstall(ctx):
+        if ctx.handle:
+            _lib.check(ctx._lib.qf_clear_forcing(ctx.handle))
+
+    # ---- the reference's `forcing(P, W) -> F` protocol, through the same kernel (pscale = s = 1)
+    def __call__(self, P, W):
+        W = np.asarray(W)
+        P = np.asarray(P)
+        if W.ndim == 3:
+            if P.ndim == 3 and P.shape[0] != W.shape[0]:
+                raise ValueError("P %s does not go with the stack W %s" % (P.shape, W.shape))
+            return np.stack([self(P[j] if P.ndim == 3 else P, W[j]) for j in range(W.shape[0])])
+        Wc = as_c128(W, "W")
+        Pc = as_c128(P, "P")
+        if Pc.shape != Wc.shape:
+            raise ValueError("operands could not be broadcast together with shapes %s %s" % (Pc.shape, Wc.shape))
+        self.check_size(Wc.shape[-1])
+        ctx = get_context(Wc.shape[-1])
+        F = np.empty_like(Wc)
+        self.install(ctx)
+        try:
+            _lib.check(ctx._lib.qf_forcing(ctx.handle, ptr(Pc), ptr(Wc), ptr(F)))
+        finally:
+            self.uninstall(ctx)
+        return F
+
+
+def forcing_installable(f):
+    """`f` is an AffineForcing and the process is in the mode in which the device follows an installed one: the
+    skew-Hermitian solve (select_skewherm(True), the default)."""
+    return isinstance(f, AffineForcing) and _SKEW_HERM_

@@ -522,10 +522,18 @@ def _device_resident_ok(integrator, kwargs):
     from . import laplacian as _lap
     if integrator not in (_int.isomp, _int.isomp_fixedpoint) and not isinstance(integrator, _int.IsompHIP):
         return False
-    if any(kwargs.get(k) is not None for k in ("forcing", "strang_splitting", "callback")):
+    if kwargs.get("callback") is not None:
         return False
-    if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim")
-           for k in kwargs):
+    # (an AffineForcing and a ViscDampStep are device objects the resident trajectory carries; any other callable is a host hook)
+    forcing, strang = kwargs.get("forcing"), kwargs.get("strang_splitting")
+    if forcing is not None and not isinstance(forcing, _lap.AffineForcing):
+        return False
+    if strang is not None and not isinstance(strang, _lap.ViscDampStep):
+        return False
+    if (forcing is not None or strang is not None) and kwargs.get("compsum"):
+        return False
+    if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim", "forcing",
+                     "strang_splitting", "callback") for k in kwargs):
         return False
     h = kwargs.get("hamiltonian")
     # (a TridiagonalHamiltonian is installed on the resident trajectory's context: as native as the built-in one)
@@ -534,7 +542,9 @@ def _device_resident_ok(integrator, kwargs):
 
 def _resident_kind(integrator, ikw, W):
     """How `solve` may keep the run on the device between its chunks, from the stepper, its keyword arguments and the state:
-    'single' (DeviceTrajectory: what _device_resident_ok admits, on an (N,N) complex128 / complex64 state), 'stack'
+    'single' (DeviceTrajectory: what _device_resident_ok admits -- the built-in or a tridiagonal Hamiltonian, no forcing or an
+    AffineForcing, no Strang step or a ViscDampStep, no callback, no compsum next to a forcing or a Strang step -- on an (N,N)
+    complex128 state, or complex64 without those device objects), 'stack'
     (DeviceStackTrajectory: isomp on a (k,N,N) complex128 stack, built-in Hamiltonian, no compsum), 'mhd'
     (DeviceMHDTrajectory: magmp with hamiltonian = solve_mhd on a (2,N,N) complex128 state) or None.  Pure: nothing is
     created or touched."""
@@ -542,7 +552,8 @@ def _resident_kind(integrator, ikw, W):
     from . import laplacian as _lap
     W = np.asarray(W)
     if W.ndim == 2:
-        ham = isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian)
+        ham = (isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian) or ikw.get('forcing') is not None
+               or ikw.get('strang_splitting') is not None)       # (device objects: complex128 only)
         ok = (_device_resident_ok(integrator, ikw) and W.shape[0] == W.shape[1]
               and W.dtype in (np.complex128, np.complex64) and (not ham or W.dtype == np.complex128))
         return 'single' if ok else None
@@ -584,7 +595,8 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
     progress_bar / progress_file: the reference's tqdm progress display (simulation.py:764-780); never
     forwarded to the integrator.  inner_steps / inner_time: the deprecated names of steps_out / dt_out.
     resident: keep the trajectory on the device between the chunks (default: whenever the stepper is
-    quflow_amd.isomp with its built-in Hamiltonian and no host hooks, on a complex128 (N,N) state or a
+    quflow_amd.isomp with its built-in or a tridiagonal Hamiltonian and no host hooks -- an AffineForcing and a ViscDampStep
+    are device objects, not hooks --, on a complex128 (N,N) state or a
     (k,N,N) stack, or quflow_amd.magmp with hamiltonian=solve_mhd on the (2,N,N) MHD state: _resident_kind).
     As in the reference the caller's array is advanced in place (isomp overwrites W) and the final
     state is returned."""
@@ -672,8 +684,13 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
     # (a complex64 state makes a single-precision resident trajectory: float32 solve, complex64 products and the
     # float32 tolerance rule, exactly what isomp does with a complex64 host array)
     ham = ikw.get('hamiltonian') if isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian) else None
+    # an AffineForcing and a ViscDampStep travel with the resident trajectory; a run with any other forcing / Strang callable
+    # (or with compsum next to them) is not resident, whatever `resident` says: the trajectory could not apply them
+    forcing, strang = ikw.get('forcing'), ikw.get('strang_splitting')
+    if (forcing is not None or strang is not None) and _resident_kind(integrator, ikw, W) != 'single':
+        use_device = False
     if use_device and W.ndim == 2 and W.dtype in (np.complex128, np.complex64) and (ham is None or W.dtype == np.complex128):
-        tr = _int.DeviceTrajectory(W, hamiltonian=ham)
+        tr = _int.DeviceTrajectory(W, hamiltonian=ham, forcing=forcing, strang_splitting=strang)
         adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "compsum", "reinitialize") if k in ikw}
     # a (k,N,N) stack under isomp, the MHD pair under magmp: resident too unless resident=False
     stack_kind = _resident_kind(integrator, ikw, W) if (resident is None or resident) and W.ndim == 3 else None
