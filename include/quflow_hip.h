@@ -156,6 +156,40 @@ int qf_clear_forcing(qf_ctx *ctx);          /* no forcing again (the buffer is k
  * qf_timer_start / qf_timer_stop: tools/forcing_resident.py). */
 int qf_forcing(qf_ctx *ctx, const void *P_host, const void *W_host, void *F_host);
 
+/* ---- stochastic band-limited forcing: the affine forcing above with a pattern F0 that is redrawn ON THE DEVICE for every
+ * step (csrc/stochastic.hip).  Over the step n -> n + 1 of size dt
+ *          F0_n = shr2mat(omega_n),   omega_n[l^2 + l + m] = (sigma_l * (1 / sqrt(dt))) * xi_n(l, m),  l_min <= l <= l_max,
+ * zero elsewhere, xi iid N(0,1): white in time, injected in a band of wavenumbers.  The generator is counter based,
+ * Philox4x32-10 (multipliers D2511F53, CD9E8D57; Weyl constants 9E3779B9, BB67AE85) with key (seed & 0xffffffff, seed >> 32)
+ * and counter (n & 0xffffffff, n >> 32, b, 0), b = q >> 1, q = l^2 + l + m.  From the output words x0..x3:
+ *          u = ((x0 >> 5) 2^26 + (x1 >> 6) + 1) 2^-53  in (0, 1],     v = ((x2 >> 5) 2^26 + (x3 >> 6)) 2^-53  in [0, 1)
+ *          r = sqrt(-2 log(u)),  t = 6.283185307179586 * v,  xi = r cos(t) for even q, r sin(t) for odd q
+ *          s = sigma_l * inv,  inv = 1.0 / sqrt(dt) formed once on the host,  omega = s * xi       (each product rounded)
+ * so a coefficient depends on (seed, n, l, m) alone: not on N, the band, how a run is cut into calls, or its neighbours.
+ * Per step: k_stoch_draw, then the pack and the slab matvec of the transforms on a band basis the context keeps -- the
+ * blocks m <= l_max, columns j <= l_max - m, 8 qf_slab_prefix(N, l_max + 1, l_max + 1) bytes (4 MB for l_max = 31 at
+ * N = 1024), built at install and kept while l_max does not change -- into the forcing's pattern buffer: F0_n has the bits
+ * of qf_shr2mat (streamed form) on the same coefficients.  The transforms' own staging buffers are not touched.
+ *   l_min, l_max   1 <= l_min <= l_max <= N - 1, else QF_ERR_INVALID
+ *   sigma          l_max - l_min + 1 amplitudes, finite and >= 0, else QF_ERR_INVALID
+ *   seed, step     the stream's key and the counter n of the next step a run takes
+ *   a_*            as qf_set_forcing
+ *   band_bytes_max the band basis may take at most this many bytes: more is QF_ERR_INVALID before anything is allocated
+ * The run's counter: a call that runs `steps` steps with the forcing installed uses the counters step .. step + steps - 1
+ * and leaves step + steps (qf_stochastic_tell); qf_stochastic_seek sets it.  qf_clear_forcing clears a stochastic forcing,
+ * qf_set_forcing replaces it.  FOLLOW: qf_isomp_forced, qf_isomp_hooked (k = 1, not magnetic, no `forcing` hook; dt > 0).
+ * REFUSE with QF_ERR_UNSUPPORTED: every entry point that refuses an affine forcing, and qf_erk_hooked (noise inside
+ * Runge-Kutta stages is out of scope) and qf_forcing (a bare evaluation has no step). */
+int qf_set_stochastic_forcing(qf_ctx *ctx, int l_min, int l_max, const double *sigma, unsigned long long seed,
+                              unsigned long long step, double a_W, double a_P, double a_lap, long long band_bytes_max);
+int qf_stochastic_tell(qf_ctx *ctx, unsigned long long *step);
+int qf_stochastic_seek(qf_ctx *ctx, unsigned long long step);
+/* The pattern of counter `step` for step size dt (> 0), without touching the run's counter: omega_host receives the
+ * (l_max + 1)^2 coefficients, F0_host the N x N complex128 pattern; either may be NULL (both: the three launches alone,
+ * queued on the context's stream without a synchronisation -- timing between qf_timer_start / qf_timer_stop).
+ * QF_ERR_STATE when no stochastic forcing is installed. */
+int qf_stochastic_pattern(qf_ctx *ctx, unsigned long long step, double dt, double *omega_host, void *F0_host);
+
 /* ---- stepper protocol: isomp_fixedpoint (quflow/integrators/isospectral.py:338-613),
  *      called by simulation.solve (quflow/simulation.py:788) ---------------------- */
 int qf_upload_W(qf_ctx *ctx, const void *W_host);     /* host -> ctx state W */

@@ -35,7 +35,7 @@ from .geometry import hbar, bracket, norm_L2, inner_L2, norm_Linf, norm_L1, inte
 from .geometry import so3_generators, cartesian_generators, rotate, rotation_matrix, grad
 from .dynamics import blob, north_blob, project_el
 from .laplacian import (solve_poisson, laplace, PoissonHIP, solve_heat, solve_helmholtz, solve_viscdamp,
-                        solve_globalqg, ViscDampStep, TridiagonalHamiltonian, coriolis, AffineForcing)
+                        solve_globalqg, ViscDampStep, TridiagonalHamiltonian, coriolis, AffineForcing, StochasticForcing)
 from .integrators import (isomp, isomp_fixedpoint, IsompHIP, DeviceTrajectory, DeviceEnsemble, DeviceStackTrajectory,
                           DeviceMHDTrajectory, euler, heun, rk4,
                           isomp_simple, isomp_quasinewton, magmp, magmp_fixedpoint, solve_mhd,

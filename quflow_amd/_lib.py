@@ -91,6 +91,11 @@ SIGNATURES = {
     "qf_set_forcing": (ctypes.c_int, [_vp, _vp, ctypes.c_ulonglong, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "qf_clear_forcing": (ctypes.c_int, [_vp]),
     "qf_forcing": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "qf_set_stochastic_forcing": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_ulonglong, ctypes.c_ulonglong,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_longlong]),
+    "qf_stochastic_tell": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "qf_stochastic_seek": (ctypes.c_int, [_vp, ctypes.c_ulonglong]),
+    "qf_stochastic_pattern": (ctypes.c_int, [_vp, ctypes.c_ulonglong, ctypes.c_double, _vp, _vp]),
     "qf_isomp_forced": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, _vp, ctypes.c_ulonglong, ctypes.POINTER(IsompStats)]),
     "qf_factor_cache_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -226,7 +226,8 @@ int qf_ctx_destroy(qf_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     void *ptrs[] = {ctx->W, ctx->dW[0], ctx->dW[1], ctx->Whalf, ctx->Phalf, ctx->PW, ctx->kahan_c, ctx->stage,
-                    ctx->lap, ctx->lap_user, ctx->poisson.tab, ctx->ham.tab, ctx->ham_offset, ctx->forcing_f0, ctx->rowpart, ctx->rowsum,
+                    ctx->lap, ctx->lap_user, ctx->poisson.tab, ctx->ham.tab, ctx->ham_offset, ctx->forcing_f0, ctx->stoch.basis, ctx->stoch.omega,
+                    ctx->stoch.stage, ctx->stoch.sigma, ctx->rowpart, ctx->rowsum,
                     ctx->t32_partial, ctx->t32_arrive, ctx->W2, ctx->Whalf2, ctx->ns_inv, ctx->ns_tmp, ctx->multi_rowpart, ctx->scalars, ctx->sk_partial, ctx->sk_flags, ctx->basis, ctx->sh_stage, ctx->sh_omega, ctx->slab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);

@@ -229,6 +229,7 @@ int qf_set_forcing(qf_ctx *ctx, const void *F0_host, unsigned long long F0_key, 
     }
     const size_t NN = (size_t)ctx->N * ctx->N;
     ctx->forcing_on = false;       // nothing is in force until the pattern is in place
+    ctx->stoch.on = false;         // (an affine forcing replaces a stochastic one)
     if (F0_host) {
         const unsigned long long fp = sample_fingerprint(static_cast<const double *>(F0_host), 2 * NN);
         if (!(ctx->forcing_f0 && F0_key != 0 && ctx->forcing_key == F0_key && ctx->forcing_fp == fp)) {
@@ -253,6 +254,7 @@ int qf_clear_forcing(qf_ctx *ctx)
     QF_TRY(check_ctx(ctx));
     ctx->forcing_on = false;
     ctx->forcing_f0_on = false;
+    ctx->stoch.on = false;
     return QF_OK;
 }
 
@@ -267,6 +269,11 @@ int qf_forcing(qf_ctx *ctx, const void *P_host, const void *W_host, void *F_host
     if (!ctx->forcing_on) {
         qf_set_error("qf_forcing: no forcing is installed (qf_set_forcing)");
         return QF_ERR_STATE;
+    }
+    if (ctx->stoch.on) {
+        qf_set_error("qf_forcing: a stochastic forcing is installed (qf_set_stochastic_forcing): its pattern belongs to a step, "
+                     "a bare evaluation has none (qf_stochastic_pattern gives the pattern of a step)");
+        return QF_ERR_UNSUPPORTED;
     }
     if (on_device)      // the kernel alone, queued on the stream: resident state, the stream-matrix buffer as it stands
         return qf_launch_forcing_affine(ctx, ctx->Phalf, ctx->W, ctx->PW, 1.0, 1.0);

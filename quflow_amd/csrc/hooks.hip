@@ -13,6 +13,8 @@
 // An AFFINE forcing installed on the context (qf_set_forcing) is no hook: k_forcing_affine forms it from Phalf and Whalf where
 // the loop would call the hook, and nothing crosses PCIe for it; qf_isomp_forced is the same loop on the context's resident
 // state (no transfer at all).
+// A STOCHASTIC forcing (qf_set_stochastic_forcing) is that affine forcing with a pattern F0 redrawn on the device at the top of
+// every step (stochastic.hip): three more launches per step, nothing else in the loop changes.
 // The two products run on the fp64 matrix cores (k_zgemm, plain stores), one pass (k_hook_assemble)
 // forms the commutator, dW, Whalf and the residual row sums, one pass (k_hook_update) the step's
 // update; the exit test reads one scalar back per iteration (the hooks synchronise the host anyway).
@@ -462,7 +464,11 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
     double time = hooks->time;
     long long total_iterations = 0, number_of_maxit = 0;
     double resnorm = 0.0;
+    const bool stochastic = dev_forced && ctx->stoch.on;
     for (int step = 0; step < steps; ++step) {
+        // a stochastic forcing: this step's pattern F0_n, n = the run's counter, drawn into forcing_f0 (three launches,
+        // stochastic.hip); constant over the step's iterations
+        if (stochastic) QF_TRY(qf_launch_stoch_pattern(ctx, ctx->stoch.step + (unsigned long long)step, dt));
         QF_TRY(strang_half());
         resnorm = std::numeric_limits<double>::infinity();          // :470
         // (`reinitialize`: dW was zeroed and Whalf = W set by the previous step's update, or is so at entry)
@@ -639,6 +645,7 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
         if (hooks->has_time) time += dt;                            // :598-599
         QF_TRY(strang_half());
     }
+    if (stochastic) ctx->stoch.step += (unsigned long long)steps;
     if (resident) QF_HIP(hipMemcpyAsync(ctx->W, S[0].W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
     for (int j = 0; j < k && !resident; ++j)
         QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].W, mbytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -695,6 +702,11 @@ int qf_erk_hooked(qf_ctx *ctx, void *W_host, int method, double dt, int steps, c
     }
     if (ctx->forcing_on && hooks->forcing) {
         qf_set_error("qf_erk_hooked: a forcing is installed on this context (qf_set_forcing) and a `forcing` hook is given as well");
+        return QF_ERR_UNSUPPORTED;
+    }
+    if (ctx->forcing_on && ctx->stoch.on) {
+        qf_set_error("qf_erk_hooked: a stochastic forcing is installed (qf_set_stochastic_forcing): noise inside Runge-Kutta "
+                     "stages is not defined here; qf_isomp_forced and qf_isomp_hooked (k = 1) follow it");
         return QF_ERR_UNSUPPORTED;
     }
     const bool dev_forced = ctx->forcing_on;       // the installed forcing: formed on the device, unscaled as the hook's is

@@ -347,6 +347,23 @@ struct qf_geom_ws {
     bool timed = false;                  // ev[] were recorded by a completed qf_so3_exp / qf_rotate
 };
 
+// The stochastic band-limited pattern of an installed forcing (qf_set_stochastic_forcing; stochastic.hip):
+// per step the coefficients omega[l^2 + l + m] = (sigma_l / sqrt(dt)) xi(seed, step, l, m), l_min <= l <= l_max, are drawn
+// on the device and F0 = shr2mat(omega) goes into ctx->forcing_f0 through the band basis.  Every buffer here is the
+// forcing's own (never ctx->sh_stage / ctx->sh_omega, whose contents the transforms' callers rely on between advances);
+// they are kept when the forcing is cleared and freed with the context.
+struct qf_stoch {
+    bool on = false;             // the installed forcing (ctx->forcing_on) draws its pattern per step
+    int l_min = 0, l_max = 0;
+    unsigned long long seed = 0, step = 0;   // key and the next step's counter of the Philox stream
+    double *basis = nullptr;     // blocks m < nmax of the quantization basis, columns j < nmax - m (k_basis_slab, m0 = 0):
+    int nmax = 0;                //   qf_slab_prefix(N, nmax, nmax) doubles, rebuilt only when the band limit nmax = l_max + 1 changes
+    double *omega = nullptr;     // nmax^2 drawn coefficients (entries below l_min^2 stay zero)
+    cplx *stage = nullptr;       // their m-major packing (k_pack_coeffs)
+    double *sigma = nullptr;     // l_max - l_min + 1 amplitudes
+    int cap = 0;                 // the band limit omega, stage and sigma were allocated for
+};
+
 struct qf_ctx {
     int N = 0;
     int device = 0;
@@ -429,6 +446,7 @@ struct qf_ctx {
     unsigned long long forcing_key = 0, forcing_fp = 0;
     bool forcing_on = false, forcing_f0_on = false;
     double forcing_aW = 0.0, forcing_aP = 0.0, forcing_alap = 0.0;
+    qf_stoch stoch;              // the stochastic pattern of the installed forcing (qf_set_stochastic_forcing), stochastic.hip
 
     // spherical-harmonics transforms (quantization.hip): basis resident in HBM, m-major staging
     double *basis = nullptr;     // N(N+1)(2N+1)/6 doubles (quantization.py:68-113), uploaded once
@@ -536,6 +554,9 @@ inline int qf_refuse_forcing(const qf_ctx *ctx, const char *who)
 // ---- hooks.hip
 // out = s * (F0 + a_W X + a_P (pscale Ph) + a_lap Delta X) of the installed forcing, in the order include/quflow_hip.h fixes
 int qf_launch_forcing_affine(qf_ctx *ctx, const cplx *Ph, const cplx *X, cplx *out, double pscale, double s);
+
+// ---- stochastic.hip: omega(step, dt) drawn into ctx->stoch.omega and F0 = shr2mat(omega) into ctx->forcing_f0 (three launches)
+int qf_launch_stoch_pattern(qf_ctx *ctx, unsigned long long step, double dt);
 
 // ---- poisson.hip
 int qf_launch_lap_table(qf_ctx *ctx, int bc, double *lap_dev);
@@ -647,6 +668,12 @@ __host__ __device__ inline long long qf_slab_prefix(int N, int Nmax, int m)
 // QF_ERR_INVALID (error set) when block 0, N x Nmax doubles, is larger than the budget.
 int qf_slab_plan(int N, int Nmax, long long slab_bytes, std::vector<int> &first, long long *max_bytes);
 int qf_launch_shr2mat(qf_ctx *ctx, int Nmax, const double *omega_dev, cplx *W_dev);
+// a band basis kept by its owner: all blocks m < Nmax as ONE slab (m0 = 0), qf_slab_prefix(N, Nmax, Nmax) doubles ...
+int qf_launch_band_basis(qf_ctx *ctx, int Nmax, double *band_dev);
+// ... and shr2mat through it: pack into `stage` (>= Nmax N complex, the caller's own), then the slab matvec.  Writes the
+// diagonals |i - j| < Nmax of W_dev and nothing else (no N^2 fill: the caller zeroed the rest once); the kernels and the
+// column arithmetic of qf_launch_shr2mat's streamed form, hence its bits.
+int qf_launch_band_shr2mat(qf_ctx *ctx, int Nmax, const double *band_dev, const double *omega_dev, cplx *stage, cplx *W_dev);
 int qf_launch_mat2shr(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev);
 int qf_launch_shc2mat(qf_ctx *ctx, const double *omega_dev, cplx *W_dev);
 int qf_launch_mat2shc(qf_ctx *ctx, const cplx *W_dev, double *omega_dev);

@@ -560,6 +560,27 @@ int qf_launch_basis(qf_ctx *ctx, double *basis_dev)
     return QF_OK;
 }
 
+int qf_launch_band_basis(qf_ctx *ctx, int Nmax, double *band_dev)
+{
+    dim3 grid((Nmax + 255) / 256, Nmax);
+    hipLaunchKernelGGL(k_basis_slab, grid, dim3(256), 0, ctx->stream, ctx->N, Nmax, 0, band_dev);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+int qf_launch_band_shr2mat(qf_ctx *ctx, int Nmax, const double *band_dev, const double *omega_dev, cplx *stage, cplx *W_dev)
+{
+    const int N = ctx->N;
+    dim3 gp((Nmax + 255) / 256, Nmax);
+    hipLaunchKernelGGL(k_pack_coeffs<MODE_SHR>, gp, dim3(256), 0, ctx->stream, N, Nmax, omega_dev, stage, (cplx *)nullptr);
+    QF_HIP(hipGetLastError());
+    dim3 gm((N + 31) / 32, Nmax);   // 32 rows per workgroup
+    hipLaunchKernelGGL((k_block_matvec<MODE_SHR, true>), gm, dim3(256), 0, ctx->stream, N, Nmax, 0, band_dev, stage,
+                       (const cplx *)nullptr, W_dev);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
 int qf_launch_shr2mat(qf_ctx *ctx, int Nmax, const double *omega_dev, cplx *W_dev) { return forward<MODE_SHR>(ctx, Nmax, omega_dev, W_dev); }
 int qf_launch_shc2mat(qf_ctx *ctx, const double *omega_dev, cplx *W_dev) { return forward<MODE_SHC>(ctx, ctx->N, omega_dev, W_dev); }
 int qf_launch_mat2shr(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev) { return backward<MODE_SHR>(ctx, Nmax, W_dev, omega_dev); }

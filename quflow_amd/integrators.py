@@ -124,8 +124,14 @@ def _hamiltonian_on(ctx, ham):
         ham.uninstall(ctx)
 
 
+def _refuse_stochastic(forcing, who):
+    """A StochasticForcing is never dropped or run as something else: the routes that do not follow it say so."""
+    if isinstance(forcing, _laplacian.StochasticForcing):
+        raise NotImplementedError("%s: %s" % (who, _laplacian._STOCHASTIC_ROUTES))
+
+
 def _installable_forcing(f, W):
-    """`f` if it is an AffineForcing that this call installs on its device context -- skew-Hermitian mode, one (N,N)
+    """`f` if it is an AffineForcing or a StochasticForcing that this call installs on its device context -- skew-Hermitian mode, one (N,N)
     complex128 state -- else None (the instance is then the host callable `forcing(P, W)` it also is)."""
     if (_laplacian.forcing_installable(f) and _SKEW_HERM_ and isinstance(W, np.ndarray) and W.ndim == 2
             and W.shape[0] == W.shape[1] and W.dtype == np.complex128):
@@ -136,8 +142,9 @@ def _installable_forcing(f, W):
 
 @contextlib.contextmanager
 def _forcing_on(ctx, aff):
-    """The call's AffineForcing installed on its context for the call alone (the twin of _hamiltonian_on): a later call on
-    the cached context must find no forcing again -- also after an error."""
+    """The call's AffineForcing / StochasticForcing installed on its context for the call alone (the twin of
+    _hamiltonian_on): a later call on the cached context must find no forcing again -- also after an error.  A
+    StochasticForcing takes its counter back from the context before it leaves (the steps the call ran)."""
     if aff is None:
         yield
         return
@@ -145,7 +152,11 @@ def _forcing_on(ctx, aff):
     try:
         yield
     finally:
-        aff.uninstall(ctx)
+        try:
+            if isinstance(aff, _laplacian.StochasticForcing):
+                aff.sync(ctx)
+        finally:
+            aff.uninstall(ctx)
 
 
 def isomp_fixedpoint(W,
@@ -518,6 +529,8 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     table = _HookTable(N, k, squeeze)
     aff = _installable_forcing(forcing, W)        # installed on the device for this call: no forcing hook
+    if aff is None:
+        _refuse_stochastic(forcing, "isomp on a stack, on complex64 data or with select_skewherm(False)")
     if forcing is not None and aff is None:
         table.set_forcing(forcing, _takes_time(forcing, (Wc, Wc), time))
     if not native:
@@ -659,6 +672,7 @@ def magmp_fixedpoint(W, dt, steps=100, hamiltonian=solve_mhd, time=None, forcing
     """
     assert minit >= 1, "minit must be at least 1."
     assert maxit >= minit, "maxit must be at minit."
+    _refuse_stochastic(forcing, "magmp")
     if not isinstance(W, np.ndarray) or W.ndim != 3 or W.shape[0] != 2 or W.shape[1] != W.shape[2]:
         raise ValueError("the MHD state must be a (2,N,N) ndarray (W, Theta)")
     steps = _reference_args(W, steps)         # (mhd.py: `for k in range(steps)`, in-place updates of the state)
@@ -697,6 +711,7 @@ def _reference_args(W, steps):
 
 
 def _check_device_stepper_args(W, hamiltonian, forcing):
+    _refuse_stochastic(forcing, "isomp_simple / isomp_quasinewton")
     if forcing is not None:
         # the reference accepts `forcing` here and never uses it (`assert NotImplementedError(...)` asserts a truthy
         # object: isospectral.py:185-186, 283-284); same result, but say so
@@ -835,6 +850,7 @@ def _erk_hooked(method, W, dt, steps, hamiltonian, forcing, device):
 
 
 def _erk(method, W, dt, steps, hamiltonian, forcing, device=None):
+    _refuse_stochastic(forcing, method)       # (noise inside Runge-Kutta stages is not defined here)
     steps = _reference_args(W, steps)         # (erk.py: `for k in range(steps)`, in-place updates of W)
     if steps == 0 and not np.issubdtype(W.dtype, np.complexfloating):
         return W                 # the reference's empty loop never touches a real / integer W
@@ -941,7 +957,8 @@ class DeviceTrajectory:
     def __init__(self, W0, device=None, hamiltonian=None, forcing=None, strang_splitting=None):
         """`hamiltonian`: None / solve_poisson for the built-in one, or a TridiagonalHamiltonian, which is installed on the
         trajectory's private context for its whole life: advance, advance_erk and advance_lu follow it.
-        `forcing`: None or an AffineForcing, installed for the trajectory's life (set_forcing replaces it between advances);
+        `forcing`: None, an AffineForcing or a StochasticForcing, installed for the trajectory's life (set_forcing replaces it
+        between advances); a StochasticForcing starts at its counter `.step` and has it advanced by every `advance`;
         `strang_splitting`: None or a ViscDampStep, the viscous / damped half step around every step.  With either one
         `advance` is the hooked loop on the resident state (qf_isomp_forced: the bits of
         isomp(W, dt, steps, forcing=..., strang_splitting=...), nothing crosses PCIe); complex128 only."""
@@ -960,8 +977,9 @@ class DeviceTrajectory:
         elif not _is_native_hamiltonian(hamiltonian):
             raise TypeError("DeviceTrajectory takes the built-in Hamiltonian or a TridiagonalHamiltonian; any other callable "
                             "runs through isomp(..., hamiltonian=...)")
-        if forcing is not None and not isinstance(forcing, _laplacian.AffineForcing):
-            raise TypeError("DeviceTrajectory takes an AffineForcing; any other callable runs through isomp(..., forcing=...)")
+        if forcing is not None and not isinstance(forcing, _laplacian.DEVICE_FORCINGS):
+            raise TypeError("DeviceTrajectory takes an AffineForcing or a StochasticForcing; any other callable runs through "
+                            "isomp(..., forcing=...)")
         if strang_splitting is not None and not isinstance(strang_splitting, _laplacian.ViscDampStep):
             raise TypeError("DeviceTrajectory takes a ViscDampStep; any other callable runs through "
                             "isomp(..., strang_splitting=...)")
@@ -992,19 +1010,38 @@ class DeviceTrajectory:
         _lib.check((self._lib.qf_c64_upload_W if self.c64 else self._lib.qf_upload_W)(self.ctx.handle, ptr(W0)))
 
     def set_forcing(self, forcing):
-        """Replace the installed forcing between advances (None: none): a run that redraws its pattern F0 per chunk."""
+        """Replace the installed forcing between advances (None: none): an AffineForcing, or a StochasticForcing, whose
+        pattern is redrawn on the device for every step from its counter `.step` on."""
         if forcing is None:
             if self.forcing is not None:
                 _laplacian.AffineForcing.uninstall(self.ctx)
             self.forcing = None
             return
-        if not isinstance(forcing, _laplacian.AffineForcing):
-            raise TypeError("DeviceTrajectory takes an AffineForcing; any other callable runs through isomp(..., forcing=...)")
+        if not isinstance(forcing, _laplacian.DEVICE_FORCINGS):
+            raise TypeError("DeviceTrajectory takes an AffineForcing or a StochasticForcing; any other callable runs through "
+                            "isomp(..., forcing=...)")
         if self.c64 or not (_SKEW_HERM_ and _laplacian._SKEW_HERM_):
             raise NotImplementedError("a resident forcing needs complex128 data and the skew-Hermitian mode "
                                       "(select_skewherm(True))")
+        forcing.check_size(self.N)
         forcing.install(self.ctx)
         self.forcing = forcing
+
+    def _stochastic(self, what):
+        if not isinstance(self.forcing, _laplacian.StochasticForcing):
+            raise ValueError("%s: no StochasticForcing is installed on this trajectory" % what)
+        return self.forcing
+
+    def stochastic_tell(self):
+        """The counter of the next step's noise, read from the device context (qf_stochastic_tell)."""
+        return self._stochastic("stochastic_tell").sync(self.ctx)
+
+    def stochastic_seek(self, step):
+        """Set the counter of the next step's noise (qf_stochastic_seek); the installed forcing's `.step` follows."""
+        f = self._stochastic("stochastic_seek")
+        step = _laplacian._uint64_arg("step", step)
+        _lib.check(self._lib.qf_stochastic_seek(self.ctx.handle, ctypes.c_ulonglong(step)))
+        f.step = step
 
     def hamiltonian_energy(self):
         """H = -inner_L2(P, W - F)/2 of the resident state with P = T^-1 (W - F) of the installed Hamiltonian (the built-in
@@ -1037,9 +1074,13 @@ class DeviceTrajectory:
             if self.strang_splitting is not None:
                 tab, key = self.strang_splitting.table_and_key(self.N, dt / 2)
                 tab = np.ascontiguousarray(tab, dtype=np.float64)
-            _lib.check(self._lib.qf_isomp_forced(self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit),
-                                                 int(bool(reinitialize)), None if tab is None else ptr(tab),
-                                                 ctypes.c_ulonglong(key), ctypes.byref(st)))
+            try:
+                _lib.check(self._lib.qf_isomp_forced(self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit),
+                                                     int(bool(reinitialize)), None if tab is None else ptr(tab),
+                                                     ctypes.c_ulonglong(key), ctypes.byref(st)))
+            finally:
+                if isinstance(self.forcing, _laplacian.StochasticForcing):
+                    self.forcing.sync(self.ctx)        # the counter the call left
             if diagnostics:
                 e, s = self.diagnostics()
                 out = {"energy": e, "enstrophy": s}
@@ -1410,6 +1451,8 @@ class DeviceEnsemble:
         assert minit >= 1, "minit must be at least 1."
         assert maxit >= minit, "maxit must be at minit."
         tol_c = -1.0 if isinstance(tol, str) else float(tol)
+        for m in self.members:
+            _refuse_stochastic(m.forcing, "DeviceEnsemble.advance")
         fn = self._lib.qf_c64_isomp_multi if self.c64 else self._lib.qf_isomp_multi
         out = []
         failed = []

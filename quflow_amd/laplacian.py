@@ -527,7 +527,239 @@ class AffineForcing:
         return F
 
 
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on uint64 arrays holding 32-bit words: `counter` four words (each a scalar or an array, broadcast
+    together), `key` two.  Returns the four output words as uint64 arrays.  The host mirror of the device generator of
+    StochasticForcing (csrc/stochastic.hip)."""
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) & _MASK32 for c in counter])
+    k0, k1 = (np.uint64(int(k) & 0xFFFFFFFF) for k in key)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2            # (32 x 32 bits: exact in uint64)
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & _MASK32, (p0 >> s32) ^ c3 ^ k1, p0 & _MASK32
+        k0 = (k0 + _PHILOX_W0) & _MASK32
+        k1 = (k1 + _PHILOX_W1) & _MASK32
+    return c0, c1, c2, c3
+
+
+def philox_uniforms(x0, x1, x2, x3):
+    """u in (0, 1] and v in [0, 1) from the four output words, every operation exact in double:
+    u = ((x0 >> 5) 2^26 + (x1 >> 6) + 1) 2^-53,  v = ((x2 >> 5) 2^26 + (x3 >> 6)) 2^-53."""
+    x0, x1, x2, x3 = (np.asarray(x, dtype=np.uint64) for x in (x0, x1, x2, x3))
+    u = ((x0 >> np.uint64(5)).astype(np.float64) * 67108864.0 + (x1 >> np.uint64(6)).astype(np.float64) + 1.0) * 2.0 ** -53
+    v = ((x2 >> np.uint64(5)).astype(np.float64) * 67108864.0 + (x3 >> np.uint64(6)).astype(np.float64)) * 2.0 ** -53
+    return u, v
+
+
+_STOCHASTIC_ROUTES = ("a StochasticForcing is followed by isomp / isomp_fixedpoint on an (N,N) complex128 host array in "
+                      "skew-Hermitian mode (select_skewherm(True)), by DeviceTrajectory(forcing=...) / .set_forcing(...) and by "
+                      "solve on such a run; elsewhere pass forcing=sf.as_callable(dt, N) to a stepper that takes a host callable")
+
+
+def _uint64_arg(name, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s must be an integer, got %r" % (name, v))
+    v = int(v)
+    if not 0 <= v < 2 ** 64:
+        raise ValueError("%s must lie in [0, 2^64), got %d" % (name, v))
+    return v
+
+
+class StochasticForcing:
+    """`forcing=` for stochastic band-limited forcing, white in time, drawn and applied on the device:
+
+        F(P, W) = F0_n + a_W W + a_P P + a_lap Delta W
+
+    where over the step n -> n + 1 of size dt the pattern is F0_n = shr2mat(omega_n, N) with
+
+        omega_n[l^2 + l + m] = (sigma_l * (1 / sqrt(dt))) * xi_n(l, m)     l_min <= l <= l_max, -l <= m <= l; zero elsewhere,
+
+    xi iid N(0,1).  The generator is counter based (Philox4x32-10, key = seed, counter = (n, (l^2 + l + m) >> 1); Box-Muller:
+    cosine for even l^2 + l + m, sine for odd; include/quflow_hip.h has every constant), so a coefficient depends on
+    (seed, n, l, m) alone -- not on N, the band, how the run is cut into calls -- and `draw_host` repeats it in numpy.  The
+    affine terms are AffineForcing's, in its order of operations; F0_n is constant over a step's fixed-point iterations.
+
+    `sigma`: one amplitude for the band or one per l (l_min .. l_max), finite and >= 0.  `seed`, `step`: integers in
+    [0, 2^64).  `.step` is the counter n of the next step a run takes: every call that ran with the forcing installed leaves
+    it advanced by its steps, and the object pickles with it -- a resumed run carries on the same noise sequence.
+
+    FOLLOWED by isomp / isomp_fixedpoint on an (N,N) complex128 host array in skew-Hermitian mode,
+    DeviceTrajectory(forcing=...) / .set_forcing(...), and solve on such runs (resident by default).  Everywhere else --
+    stacks, magmp, complex64, select_skewherm(False), euler / heun / rk4, isomp_simple / isomp_quasinewton, DeviceEnsemble --
+    it raises NotImplementedError; `as_callable(dt, N)` is the host callable with the same numbers for those routes."""
+
+    def __init__(self, l_min, l_max, sigma, seed, a_W=0.0, a_P=0.0, a_lap=0.0, step=0):
+        for name, v in (("l_min", l_min), ("l_max", l_max)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an integer, got %r" % (name, v))
+        l_min, l_max = int(l_min), int(l_max)
+        if not 1 <= l_min <= l_max:
+            raise ValueError("the band must satisfy 1 <= l_min <= l_max (l = 0 is the trace), got l_min=%d, l_max=%d"
+                             % (l_min, l_max))
+        if l_max > 8191:
+            raise ValueError("l_max must be at most 8191 (N <= 8192), got %d" % l_max)
+        if sigma is None or isinstance(sigma, (str, bytes, bool)) or np.iscomplexobj(sigma):
+            raise TypeError("sigma must be a real number or one real number per l of the band, got %r" % (sigma,))
+        try:
+            sig = np.array(sigma, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError("sigma must be a real number or one real number per l of the band, got %r" % (sigma,))
+        nl = l_max - l_min + 1
+        if sig.ndim == 0:
+            sig = np.full(nl, float(sig))
+        if sig.shape != (nl,):
+            raise ValueError("sigma must be a scalar or have one value per l of the band (%d), got shape %s" % (nl, sig.shape))
+        if not np.all(np.isfinite(sig)) or np.any(sig < 0):
+            raise ValueError("sigma must be finite and >= 0")
+        coeff = []
+        for name, a in (("a_W", a_W), ("a_P", a_P), ("a_lap", a_lap)):
+            if isinstance(a, (complex, np.complexfloating)) or isinstance(a, (str, bytes, bool)) or not np.isscalar(a):
+                raise TypeError("%s must be a real number, got %r" % (name, a))
+            a = float(a)
+            if not np.isfinite(a):
+                raise ValueError("%s must be finite, got %r" % (name, a))
+            coeff.append(a)
+        self.l_min, self.l_max = l_min, l_max
+        self.sigma = np.ascontiguousarray(sig)
+        self.sigma.setflags(write=False)
+        self.seed = _uint64_arg("seed", seed)
+        self.step = _uint64_arg("step", step)
+        self.a_W, self.a_P, self.a_lap = coeff
+
+    def check_size(self, N):
+        if self.l_max > int(N) - 1:
+            raise ValueError("the band reaches l_max=%d, a state of size N=%d carries l <= %d" % (self.l_max, int(N), int(N) - 1))
+
+    # ---- installing on a device context (the steppers and the device objects call these)
+    def install(self, ctx):
+        from .quantization import slab_bytes
+        self.check_size(ctx.N)
+        sig = np.array(self.sigma)
+        _lib.check(ctx._lib.qf_set_stochastic_forcing(ctx.handle, self.l_min, self.l_max, ptr(sig), ctypes.c_ulonglong(self.seed),
+                                                      ctypes.c_ulonglong(self.step), self.a_W, self.a_P, self.a_lap,
+                                                      ctypes.c_longlong(slab_bytes())))
+
+    def sync(self, ctx):
+        """Read the counter back from the context this forcing is installed on (qf_stochastic_tell)."""
+        n = ctypes.c_ulonglong()
+        _lib.check(ctx._lib.qf_stochastic_tell(ctx.handle, ctypes.byref(n)))
+        self.step = int(n.value)
+        return self.step
+
+    @staticmethod
+    def uninstall(ctx):
+        if ctx.handle:
+            _lib.check(ctx._lib.qf_clear_forcing(ctx.handle))
+
+    def __call__(self, *args, **kwargs):
+        raise NotImplementedError("a StochasticForcing is no host callable forcing(P, W): " + _STOCHASTIC_ROUTES)
+
+    # ---- what the device draws, downloaded (qf_stochastic_pattern); the run's counter is not touched
+    def _device_pattern(self, n, dt, N, want_pattern):
+        n = _uint64_arg("n", n)
+        N = int(N)
+        self.check_size(N)
+        ctx = get_context(N)
+        omega = np.zeros((self.l_max + 1) ** 2, dtype=np.float64)
+        F0 = np.zeros((N, N), dtype=np.complex128) if want_pattern else None
+        self.install(ctx)
+        try:
+            _lib.check(ctx._lib.qf_stochastic_pattern(ctx.handle, ctypes.c_ulonglong(n), float(dt), ptr(omega),
+                                                      None if F0 is None else ptr(F0)))
+        finally:
+            self.uninstall(ctx)
+        return omega, F0
+
+    def coefficients(self, n, dt, N):
+        """omega_n for step size dt as the device draws it: (l_max + 1)^2 real coefficients, index l^2 + l + m."""
+        return self._device_pattern(n, dt, N, False)[0]
+
+    def pattern(self, n, dt, N):
+        """F0_n = shr2mat(omega_n, N) as the device forms it for the run: an (N,N) complex128 skew-Hermitian matrix."""
+        return self._device_pattern(n, dt, N, True)[1]
+
+    def draw_host(self, n, dt):
+        """The numpy mirror of the device draw: omega_n, (l_max + 1)^2 doubles.  Philox on uint64 arrays, then the formulas
+        of the class docstring, operation by operation; differs from `coefficients` only by the device's log / sincos
+        against numpy's."""
+        n = _uint64_arg("n", n)
+        dt = float(dt)
+        if not dt > 0.0 or not np.isfinite(dt):
+            raise ValueError("dt must be positive and finite, got %r" % dt)
+        q = np.arange(self.l_min ** 2, (self.l_max + 1) ** 2, dtype=np.int64)
+        x = philox4x32_10((n & 0xFFFFFFFF, n >> 32, (q >> 1).astype(np.uint64), 0), (self.seed & 0xFFFFFFFF, self.seed >> 32))
+        u, v = philox_uniforms(*x)
+        r = np.sqrt(-2.0 * np.log(u))
+        t = 6.283185307179586 * v
+        xi = np.where(q % 2 == 0, r * np.cos(t), r * np.sin(t))
+        el = np.floor(np.sqrt(q.astype(np.float64))).astype(np.int64)      # (q < 2^26: the double root floors exactly)
+        inv = 1.0 / np.sqrt(dt)
+        s = self.sigma[el - self.l_min] * inv
+        omega = np.zeros((self.l_max + 1) ** 2, dtype=np.float64)
+        omega[q] = s * xi
+        return omega
+
+    def as_callable(self, dt, N, time0=0.0):
+        """The time-dependent host callable f(P, W, time) with this forcing's numbers, for the routes the device does not
+        follow (pass `time=` to the stepper).  A stepper evaluates the forcing of the step that starts at time t at
+        t + dt/2, so the step index is n = step + round((time - time0 - dt/2) / dt), clamped at 0, with `step` the counter at
+        the time of this call and time0 the time of that step's start; the pattern is pattern(n, dt, N), then the affine
+        lines in AffineForcing's order.  A pure function of its arguments: a stepper's probing call consumes nothing."""
+        dt, N, time0, step0 = float(dt), int(N), float(time0), self.step
+        self.check_size(N)
+        a_W, a_P, a_lap = self.a_W, self.a_P, self.a_lap
+        last = {}
+
+        def forcing(P, W, time):
+            W = np.asarray(W)
+            if W.ndim == 3:
+                P = np.asarray(P)
+                return np.stack([forcing(P[j] if P.ndim == 3 else P, W[j], time) for j in range(W.shape[0])])
+            n = max(step0 + int(round((float(time) - time0 - dt / 2) / dt)), 0)
+            if last.get("n") != n:
+                last["F0"] = self.pattern(n, dt, N)
+                last["n"] = n
+            F0 = last["F0"]
+            fr, fi = F0.real.copy(), F0.imag.copy()
+            if a_W != 0.0:
+                fr = fr + a_W * W.real
+                fi = fi + a_W * W.imag
+            if a_P != 0.0:
+                fr = fr + a_P * P.real
+                fi = fi + a_P * P.imag
+            if a_lap != 0.0:
+                L = laplace(np.ascontiguousarray(W, dtype=np.complex128))
+                fr = fr + a_lap * L.real
+                fi = fi + a_lap * L.imag
+            out = np.empty(W.shape, dtype=np.complex128)
+            out.real = fr
+            out.imag = fi
+            return out
+        return forcing
+
+    # ---- expected injection rates.  The basis elements T_lm (elmr2mat) have unit norm_L2 and Delta T_lm = -l(l+1) T_lm, so
+    # over one step dt F0_n = sqrt(dt) sum sigma_l xi T_lm adds on average dt/2 sum_l (2l+1) sigma_l^2 of enstrophy
+    # <W, W>/2 and dt/2 sum_l (2l+1) sigma_l^2 / (l(l+1)) of energy -<W, Delta^-1 W>/2 (the cross terms vanish in the mean)
+    def energy_rate(self):
+        """Expected energy injection per unit time: 1/2 sum_l (2l + 1) sigma_l^2 / (l (l + 1))."""
+        el = np.arange(self.l_min, self.l_max + 1, dtype=np.float64)
+        return float(0.5 * np.sum((2 * el + 1) * self.sigma ** 2 / (el * (el + 1))))
+
+    def enstrophy_rate(self):
+        """Expected enstrophy injection per unit time: 1/2 sum_l (2l + 1) sigma_l^2."""
+        el = np.arange(self.l_min, self.l_max + 1, dtype=np.float64)
+        return float(0.5 * np.sum((2 * el + 1) * self.sigma ** 2))
+
+
+DEVICE_FORCINGS = (AffineForcing, StochasticForcing)      # what a device context follows once installed
+
+
 def forcing_installable(f):
-    """`f` is an AffineForcing and the process is in the mode in which the device follows an installed one: the
-    skew-Hermitian solve (select_skewherm(True), the default)."""
-    return isinstance(f, AffineForcing) and _SKEW_HERM_
+    """`f` is an AffineForcing or a StochasticForcing and the process is in the mode in which the device follows an installed
+    one: the skew-Hermitian solve (select_skewherm(True), the default)."""
+    return isinstance(f, DEVICE_FORCINGS) and _SKEW_HERM_
