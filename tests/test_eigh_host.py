@@ -27,6 +27,24 @@ cannot empty the bar, the inputs are chosen to have ||P||_2 / gap <= GAP_CAP = 2
 tests -- and every test that uses them asserts it.
 
 Every ratio is the worst over ref_samples(N) seeded inputs per size and kind (8 up to N = 5, where the worst ratios sit, 2 up to N = 33, one above).
+
+Run sizes (tests/test_hip_eigh_large.py).  The worst ratios above sit at N = 2 and 3, and one constant for every N carries
+them up: at N = 1024 LAPACK is some fifty times below them.  So the sizes that runs use get records of their own,
+RATIO_ORTH_LARGE, RATIO_RES_LARGE and RATIO_LAM_LARGE: numpy.linalg.eigh on structured(N, kind) -- a known spectrum under
+two seeded Householder reflections and a diagonal of phases, built in long double and rounded once -- in every kind at
+N = 1024 and on `decay` at N = 2049.  Above LD_MAX = 257 an error is evaluated in fp64 (a long double product takes minutes
+there); the reference is measured with the same evaluation, so its rounding is in both.  The device bar at these sizes is
+min(C_X, 8 RATIO_X_LARGE).
+
+Two more measures hold the COEFFICIENTS of the scale decomposition, which skew-Hermitian symmetry, Wr = W - Ws and
+[P, Ws] = 0 leave free (they hold for V diag(d) V^H with any imaginary d; test_wrong_coefficients_are_caught shows it):
+
+  Frobenius orthogonality   |Re<Ws, Wr>_F| / (N eps |W|_F^2)                       RATIO_FROB   (device bar: 8 RATIO_FROB)
+  idempotence               max|Ws(Ws, P) - Ws(W, P)| / (N eps ||W||_2)            RATIO_IDEM   (device bar: 8 RATIO_IDEM)
+
+W -> Ws is the orthogonal projection, in the Frobenius inner product, onto the matrices diagonal in P's eigenbasis: Ws and
+Wr are orthogonal exactly when d_j = v_j^H W v_j, and projecting twice changes nothing.  Neither measure carries the gap
+factor, so both also apply to the stream matrix of a smooth state (smooth_case), whose eigenvalues nearly coincide.
 """
 import functools
 import inspect
@@ -54,6 +72,27 @@ C_LAM = 8 * RATIO_LAM
 C_SD = 8 * RATIO_SD
 C_COMM = 8 * RATIO_COMM
 GAP_CAP = 2000.0
+
+# run sizes: numpy.linalg.eigh on structured(N, kind), errors evaluated in fp64 (see test_reference_large_structured)
+LD_MAX = 257
+STRUCTURED_KINDS = ("decay", "clusters", "rank one")
+LARGE_CASES = tuple((1024, kind) for kind in STRUCTURED_KINDS) + ((2049, "decay"),)
+RATIO_ORTH_LARGE = 0.028    # measured 0.0273 on decay at N = 1024 (clusters 0.0205, rank one 0.0254; decay at N = 2049 0.0195)
+RATIO_RES_LARGE = 0.021     # measured 0.0202 on decay at N = 1024 (clusters 0.0119, rank one 0.0005; decay at N = 2049 0.0075)
+RATIO_LAM_LARGE = 0.020     # measured 0.0193 on clusters at N = 1024 (decay 0.0186, rank one 0.0001; decay at N = 2049 0.0076)
+# numpy's residual and eigenvalue ratios per case (measured 0.0202, 0.0119, 0.0005, 0.0075 and 0.0186, 0.0193, 0.0001, 0.0076;
+# rounded up), for the device-to-numpy figures that the device tests print
+NUMPY_RES_LARGE = {(1024, "decay"): 0.021, (1024, "clusters"): 0.012, (1024, "rank one"): 0.0006, (2049, "decay"): 0.0076}
+NUMPY_LAM_LARGE = {(1024, "decay"): 0.019, (1024, "clusters"): 0.020, (1024, "rank one"): 0.0002, (2049, "decay"): 0.0077}
+C_ORTH_LARGE = min(C_ORTH, 8 * RATIO_ORTH_LARGE)
+C_RES_LARGE = min(C_RES, 8 * RATIO_RES_LARGE)
+C_LAM_LARGE = min(C_LAM, 8 * RATIO_LAM_LARGE)
+# the coefficients of the scale decomposition (see test_reference_scale_decomposition_coefficients)
+SMOOTH_SIZES = (64, 130, 1024)
+RATIO_FROB = 0.79           # measured 0.789 at N = 3 (0.43 at N = 2, 0.25 at N = 5, 0.03 at N = 16, below 0.003 from N = 31 on; smooth: 0.030 at N = 64, 0.006 at 130, 0.0003 at 1024)
+RATIO_IDEM = 1.16           # measured 1.151 at N = 3 (0.84 at N = 2, 0.62 at N = 5, 0.15 at N = 16, below 0.02 from N = 31 on; smooth: 0.033 at N = 64, 0.024 at 130, 0.003 at 1024)
+C_FROB = 8 * RATIO_FROB
+C_IDEM = 8 * RATIO_IDEM
 SD_SEEDS = {2: 200, 3: 300, 5: 500, 16: 1600, 31: 3100, 32: 3200, 33: 3300, 64: 6400, 65: 6500, 130: 13000, 256: 25600}
 
 
@@ -145,6 +184,82 @@ def sd_case(N, k=0):
     return skew(N, 500000 + seed), P, g
 
 
+def structured_spectrum(N, kind):
+    """The spectrum d of structured(N, kind), in the order it is laid on the diagonal.
+    decay:     d_j = (-1)^j 2^(-70 floor(j/2) / floor(N/2)): both signs over 21 decades; what lies below eps |H| (about
+               a quarter of it) becomes one exact cluster under the solver's shift
+    clusters:  clustered()'s 1, 0, -2 in thirds
+    rank one:  e_0, an (N-1)-fold eigenvalue 0"""
+    j = np.arange(N)
+    if kind == "decay":
+        return (-1.0) ** j * 2.0 ** (-70.0 * (j // 2) / (N // 2))
+    d = np.zeros(N)
+    if kind == "clusters":
+        d[:N // 3] = 1.0
+        d[2 * (N // 3):] = -2.0
+    elif kind == "rank one":
+        d[0] = 1.0
+    else:
+        raise ValueError(kind)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def structured(N, kind):
+    """(H, lam_exact): H = Phi R2 R1 diag(d) R1^H R2^H Phi^H with the reflections R_k = I - 2 u_k u_k^H (seeded complex
+    unit vectors) and Phi = diag(exp(i theta_j)) (seeded phases), formed in long double by rank-two updates -- O(N^2) --
+    its Hermitian part rounded once to complex128; lam_exact = sort(d).  Cached and read-only."""
+    d = structured_spectrum(N, kind)
+    rng = np.random.default_rng(7000 * N + STRUCTURED_KINDS.index(kind))
+    M = np.zeros((N, N), dtype=CLD)
+    M[np.arange(N), np.arange(N)] = d
+    for _ in range(2):
+        u = (rng.standard_normal(N) + 1j * rng.standard_normal(N)).astype(CLD)
+        u /= np.sqrt((u.real ** 2 + u.imag ** 2).sum())
+        M -= 2 * np.outer(u, u.conj() @ M)          # R M
+        M -= 2 * np.outer(M @ u, u.conj())          # (R M) R^H
+    theta = rng.uniform(0.0, 2 * np.pi, N).astype(LD)
+    phi = np.cos(theta) + 1j * np.sin(theta)
+    M = phi[:, None] * M * phi.conj()[None, :]
+    H = ((M + M.conj().T) / 2).astype(np.complex128)
+    assert np.abs(H - H.conj().T).max() == 0.0
+    # complex entries of every phase, so that a missing conjugate fails.  (Compared off the diagonal: the diagonal of a
+    # Hermitian matrix is real, and here it carries d itself, N times the size of the entries the reflections spread.)
+    off = H - np.diag(np.diag(H))
+    assert np.abs(off.imag).max() > 0.5 * np.abs(off.real).max() > 0.0, (N, kind)
+    lam = np.sort(d)
+    H.setflags(write=False)
+    lam.setflags(write=False)
+    return H, lam
+
+
+def shuffled_diagonal(N):
+    """(H, d): the real diagonal matrix of the distinct entries j + 1 - N/2, j < N, in seeded random order."""
+    d = np.random.default_rng(9000 + N).permutation(N) + 1.0 - N // 2
+    return np.diag(d).astype(complex), d
+
+
+@functools.lru_cache(maxsize=None)
+def smooth_state(N, seed=1):
+    """The smooth state oracle.make_W0_smooth(N, seed) of the stepper tests (read-only): the data runs start from."""
+    from oracle import isomp_oracle
+    W = isomp_oracle.make_W0_smooth(N, seed)
+    assert np.abs(W + W.conj().T).max() == 0.0
+    W.setflags(write=False)
+    return W
+
+
+@functools.lru_cache(maxsize=None)
+def smooth_case(N, seed=1):
+    """(W, P): smooth_state and its stream matrix by the CPU oracle's solve_poisson (the device tests take the device's)."""
+    from oracle import isomp_oracle
+    W = smooth_state(N, seed)
+    P = isomp_oracle.solve_poisson(W).copy()        # (the oracle returns the same buffer on every call)
+    assert np.abs(P + P.conj().T).max() == 0.0
+    P.setflags(write=False)
+    return W, P
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # error measures (long double by default)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -196,6 +311,30 @@ def ws_eig_numpy(W, P):
     EWE = E.conj().T @ W @ E
     D2 = np.diag(np.diag(EWE))
     return E @ D2 @ E.conj().T
+
+
+def eigh_ratios(H, lam, V, lam_exact):
+    """(orthogonality, residual, known spectrum) of a decomposition of a matrix whose spectrum is known, as ratios to
+    N eps, N eps ||H||_2 and N eps max|lam_exact| with ||H||_2 = max|lam_exact|; long double up to LD_MAX, fp64 above."""
+    N = H.shape[0]
+    ld = N <= LD_MAX
+    top = float(np.abs(lam_exact).max())
+    return (orth_err(V, ld) / (N * EPS), res_err(H, lam, V, ld) / (N * EPS * top),
+            float(np.abs(lam - lam_exact).max()) / (N * EPS * top))
+
+
+def frob_orth(W, Ws, Wr):
+    """|Re<Ws, Wr>_F| / |W|_F^2, summed in long double (O(N^2) at every size)."""
+    inner = (Ws.real.astype(LD) * Wr.real.astype(LD) + Ws.imag.astype(LD) * Wr.imag.astype(LD)).sum()
+    return float(abs(inner) / (W.real.astype(LD) ** 2 + W.imag.astype(LD) ** 2).sum())
+
+
+def sd_coefficient_ratios(W, P, decompose):
+    """(Frobenius orthogonality / (N eps), idempotence / (N eps ||W||_2)) of Ws = decompose(W, P)."""
+    N = W.shape[0]
+    Ws = decompose(W, P)
+    again = decompose(Ws, P)
+    return frob_orth(W, Ws, W - Ws) / (N * EPS), float(np.abs(again - Ws).max()) / (N * EPS * norm2(W))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -263,6 +402,76 @@ def test_reference_scale_decomposition():
     print("worst %.3f (RATIO_SD %.2f), commutation %.3f (RATIO_COMM %.2f)" % (worst, RATIO_SD, worst_c, RATIO_COMM))
     assert worst <= RATIO_SD
     assert worst_c <= RATIO_COMM
+
+
+def test_structured_inputs():
+    """What structured() promises, where long double can still check it: the spectrum of H is the one laid in."""
+    for kind in STRUCTURED_KINDS:
+        for N in (5, 64, 130):
+            H, exact = structured(N, kind)
+            assert H.dtype == np.complex128 and np.all(np.diff(exact) >= 0)
+            assert np.array_equal(exact, np.sort(structured_spectrum(N, kind)))
+            r = float(np.abs(np.linalg.eigvalsh(H) - exact).max()) / (N * EPS * np.abs(exact).max())
+            print("structured %-8s N=%4d  numpy eigvalsh against the spectrum laid in: err/(N eps max|lam|) = %.3f" % (kind, N, r))
+            assert r <= RATIO_LAM
+    d = structured_spectrum(1024, "decay")
+    assert d[0] == 1.0 and d[1] == -1.0 and np.abs(d).min() < 1e-20 and 0.2 < np.mean(np.abs(d) < EPS) < 0.3
+    H, d = shuffled_diagonal(1024)
+    assert np.unique(d).size == 1024 and np.any(np.diff(d) < 0) and np.array_equal(np.diag(H).real, d)
+
+
+def test_reference_large_structured():
+    """RATIO_*_LARGE: numpy.linalg.eigh at the sizes runs use, evaluated as the device's results are."""
+    worst = [0.0, 0.0, 0.0]
+    for N, kind in LARGE_CASES:
+        H, exact = structured(N, kind)
+        lam, V = np.linalg.eigh(H)
+        r = eigh_ratios(H, lam, V, exact)
+        print("numpy eigh, structured %-8s N=%4d (fp64 evaluation)  orth/(N eps) = %.4f   res/(N eps ||H||) = %.4f   "
+              "lam/(N eps max|lam|) = %.4f" % (kind, N, r[0], r[1], r[2]))
+        worst = [max(a, b) for a, b in zip(worst, r)]
+        assert r[1] <= NUMPY_RES_LARGE[(N, kind)] and r[2] <= NUMPY_LAM_LARGE[(N, kind)], (N, kind, r)
+    print("worst: orth %.4f (RATIO_ORTH_LARGE %.3f), res %.4f (RATIO_RES_LARGE %.3f), lam %.4f (RATIO_LAM_LARGE %.3f)"
+          % (worst[0], RATIO_ORTH_LARGE, worst[1], RATIO_RES_LARGE, worst[2], RATIO_LAM_LARGE))
+    assert worst[0] <= RATIO_ORTH_LARGE and worst[1] <= RATIO_RES_LARGE and worst[2] <= RATIO_LAM_LARGE
+    assert C_ORTH_LARGE <= C_ORTH and C_RES_LARGE <= C_RES and C_LAM_LARGE <= C_LAM
+
+
+def test_reference_scale_decomposition_coefficients():
+    """RATIO_FROB, RATIO_IDEM: the numpy eigh form on the white cases and on smooth states."""
+    worst_f = worst_i = 0.0
+    for what, sizes in (("white", SIZES), ("smooth", SMOOTH_SIZES)):
+        for N in sizes:
+            f = i = 0.0
+            for k in range(ref_samples(N) if what == "white" else 1):
+                W, P = sd_case(N, k)[:2] if what == "white" else smooth_case(N)
+                rf, ri = sd_coefficient_ratios(W, P, ws_eigh_numpy)
+                f, i = max(f, rf), max(i, ri)
+            print("scale decomposition, %-6s N=%4d   |Re<Ws, Wr>|/(N eps |W|_F^2) = %.4f   idempotence/(N eps ||W||) = %.4f" % (what, N, f, i))
+            worst_f, worst_i = max(worst_f, f), max(worst_i, i)
+    print("worst: Frobenius orthogonality %.4f (RATIO_FROB %.3f), idempotence %.4f (RATIO_IDEM %.3f)" % (worst_f, RATIO_FROB, worst_i, RATIO_IDEM))
+    assert worst_f <= RATIO_FROB
+    assert worst_i <= RATIO_IDEM
+
+
+def test_wrong_coefficients_are_caught():
+    """V diag(d) V^H with numpy's eigenvectors of P and seeded RANDOM imaginary d of the right size is skew-Hermitian and
+    commutes with P as well as the true Ws does -- it passes every property the device tests asserted before these
+    measures -- and misses the Frobenius orthogonality bar by many orders of magnitude."""
+    for N in (256, 1024):
+        W, P = smooth_case(N)
+        ld = N <= LD_MAX
+        _, E = np.linalg.eigh(-1j * P)
+        true_d = np.einsum("ij,ij->j", E.conj(), W @ E)
+        d = 1j * np.random.default_rng(N).standard_normal(N) * np.sqrt(np.mean(np.abs(true_d) ** 2))
+        Ws = (E * d[None, :]) @ E.conj().T
+        Ws = (Ws - Ws.conj().T) / 2
+        comm = comm_err(P, Ws, ld) / (N * EPS * norm2(P) * norm2(W))
+        frob = frob_orth(W, Ws, W - Ws) / (N * EPS)
+        print("random coefficients, smooth N=%4d: commutation ratio %.4f (RATIO_COMM %.2f: passes), Frobenius orthogonality "
+              "ratio %.3e (bar %.3f: caught)" % (N, comm, RATIO_COMM, frob, C_FROB))
+        assert comm <= RATIO_COMM
+        assert frob > 1e6 * C_FROB
 
 
 # ---------------------------------------------------------------------------------------------------------------------
