@@ -1,6 +1,6 @@
-// C ABI of libquflow_hip.so, part 4 of 5: the OTHER steppers on the same kernels -- euler / heun / rk4
-// (quflow/integrators/erk.py), isomp_simple / isomp_quasinewton (isospectral.py:155-335), isomp / magmp on stacks of
-// states (host loop per iteration).
+// C ABI of libquflow_hip.so, part 4 of 5: the OTHER steppers on the same kernels -- isomp_simple / isomp_quasinewton
+// (isospectral.py:155-335), isomp / magmp on stacks of states (host loop per iteration) and the resident stack.
+// (euler / heun / rk4: api_erk.hip.)
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -12,144 +12,6 @@
 #include "qf_api.h"
 
 extern "C" {
-
-// (quflow/geometry.py:41-49).  For skew-Hermitian data X@P = (P@X)^H: one product per stage.
-int qf_erk(qf_ctx *ctx, int method, double dt, int steps, int skewh)
-{
-    QF_TRY(check_ctx(ctx));
-    if (method < QF_ERK_EULER || method > QF_ERK_RK4) {
-        qf_set_error("qf_erk: unknown method %d", method);
-        return QF_ERR_INVALID;
-    }
-    if (steps < 0) {
-        qf_set_error("qf_erk: steps must be >= 0");
-        return QF_ERR_INVALID;
-    }
-    QF_TRY(qf_refuse_forcing(ctx, "qf_erk"));
-    const double inv_hb = 1.0 / qf_hbar(ctx->N);
-    ctx->w_skew_known = false;
-    bool one_product = false;
-    if (skewh) {
-        QF_TRY(qf_launch_skew_defect(ctx, ctx->W, ctx->scalars + 4));
-        QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        QF_HIP(hipStreamSynchronize(ctx->stream));
-        one_product = (ctx->host_scalars[0] == 0.0);
-    }
-    cplx *W = ctx->W, *Wp = ctx->Whalf, *P = ctx->Phalf, *A = ctx->PW, *B = ctx->stage, *acc = ctx->dW[0];
-    // K(X) into the stage kernel: products of P = Delta^-1 X with X
-    auto products = [&](const cplx *X) -> int {
-        {
-            prof_scope p(ctx, QF_KERNEL_POISSON);
-            if (skewh) QF_TRY(qf_launch_hamiltonian(ctx, X, P, 1.0));
-            else QF_TRY(qf_launch_solve(ctx, ctx->poisson, X, P, 1.0, 0));
-        }
-        {
-            prof_scope p(ctx, QF_KERNEL_GEMM1);
-            QF_TRY(qf_launch_zgemm(ctx, P, X, A, nullptr));
-        }
-        if (!one_product) {
-            prof_scope p(ctx, QF_KERNEL_GEMM2);
-            QF_TRY(qf_launch_zgemm(ctx, X, P, B, nullptr));
-        }
-        return QF_OK;
-    };
-    const cplx *Bk = one_product ? nullptr : B;
-    auto stage = [&](cplx *acc_, double c_acc, cplx *Wp_, double c_wp, cplx *Wout_, double c_fin) -> int {
-        prof_scope p(ctx, QF_KERNEL_UPDATE);
-        return qf_launch_erk_stage(ctx, A, Bk, inv_hb, W, acc_, c_acc, Wp_, c_wp, Wout_, c_fin);
-    };
-    for (int k = 0; k < steps; ++k) {
-        if (method == QF_ERK_EULER) {           // erk.py:53-56
-            QF_TRY(products(W));
-            QF_TRY(stage(nullptr, 0.0, nullptr, 0.0, W, dt));
-        } else if (method == QF_ERK_HEUN) {     // erk.py:91-110
-            QF_TRY(products(W));
-            QF_TRY(stage(acc, 0.0, Wp, dt, nullptr, 0.0));            // F0; Wprime = W + dt*F0
-            QF_TRY(products(Wp));
-            QF_TRY(stage(acc, 1.0, nullptr, 0.0, W, dt / 2.0));       // F += F0; F *= dt/2; W += F
-        } else {                                // erk.py:139-156
-            QF_TRY(products(W));
-            QF_TRY(stage(acc, 0.0, Wp, dt / 2.0, nullptr, 0.0));      // K1
-            QF_TRY(products(Wp));
-            QF_TRY(stage(acc, 2.0, Wp, dt / 2.0, nullptr, 0.0));      // K1 + 2 K2
-            QF_TRY(products(Wp));
-            QF_TRY(stage(acc, 2.0, Wp, dt, nullptr, 0.0));            // ... + 2 K3
-            QF_TRY(products(Wp));
-            QF_TRY(stage(acc, 1.0, nullptr, 0.0, W, dt / 6.0));       // ... + K4; W += (dt/6) * (...)
-        }
-    }
-    QF_HIP(hipStreamSynchronize(ctx->stream));
-    return QF_OK;
-}
-
-// euler / heun / rk4 on a stack of k states (erk.py:19-160 with W.shape = (k,N,N)): the Hamiltonian reads state 0
-// (solve_poisson reduces a stack to its first state, cpu.py:672-674,696-697) and bracket(P, W) broadcasts the one
-// stream matrix over the stack (geometry.py:41-49: P@W - W@P with numpy's batched matmul) -- every state is
-// advected by state 0's flow, stage by stage.  Host in / host out.
-int qf_erk_states(qf_ctx *ctx, void *states_host, int k, int method, double dt, int steps, int skewh)
-{
-    QF_TRY(check_ctx(ctx));
-    if (method < QF_ERK_EULER || method > QF_ERK_RK4 || steps < 0 || k < 1 || !states_host) {
-        qf_set_error("qf_erk_states: bad arguments (method %d, steps %d, k %d)", method, steps, k);
-        return QF_ERR_INVALID;
-    }
-    QF_TRY(qf_refuse_forcing(ctx, "qf_erk_states"));
-    const int N = ctx->N;
-    const size_t mbytes = (size_t)N * N * sizeof(cplx);
-    const double inv_hb = 1.0 / qf_hbar(N);
-    while (ctx->multi.size() < (size_t)3 * k) {          // per state: X (state), Xp (stage argument), acc
-        cplx *p = nullptr;
-        QF_HIP(hipMalloc((void **)&p, mbytes));
-        ctx->multi.push_back(p);
-    }
-    struct st { cplx *X, *Xp, *acc; };
-    std::vector<st> S((size_t)k);
-    bool one_product = skewh != 0;
-    for (int j = 0; j < k; ++j) {
-        S[j].X = ctx->multi[3 * j];
-        S[j].Xp = ctx->multi[3 * j + 1];
-        S[j].acc = ctx->multi[3 * j + 2];
-        QF_HIP(hipMemcpyAsync(S[j].X, (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
-        if (one_product) {       // X@P = (P@X)^H needs every state exactly skew-Hermitian
-            QF_TRY(qf_launch_skew_defect(ctx, S[j].X, ctx->scalars + 4));
-            QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            QF_HIP(hipStreamSynchronize(ctx->stream));
-            one_product = (ctx->host_scalars[0] == 0.0);
-        }
-    }
-    cplx *P = ctx->Phalf, *A = ctx->PW, *B = ctx->stage;
-    // one stage for the whole stack: P from the stage argument of state 0, then every state's slope
-    auto stage_all = [&](bool from_state, double c_acc, bool want_wp, double c_wp, bool fin, double c_fin) -> int {
-        if (skewh) QF_TRY(qf_launch_hamiltonian(ctx, from_state ? S[0].X : S[0].Xp, P, 1.0));
-        else QF_TRY(qf_launch_solve(ctx, ctx->poisson, from_state ? S[0].X : S[0].Xp, P, 1.0, 0));
-        // (P is complete before state 0's stage overwrites its stage argument; the other states need only P)
-        for (int j = 0; j < k; ++j) {
-            const cplx *Xarg = from_state ? S[j].X : S[j].Xp;
-            QF_TRY(qf_launch_zgemm(ctx, P, Xarg, A, nullptr));
-            if (!one_product) QF_TRY(qf_launch_zgemm(ctx, Xarg, P, B, nullptr));
-            QF_TRY(qf_launch_erk_stage(ctx, A, one_product ? nullptr : B, inv_hb, S[j].X, c_acc == 0.0 && !want_wp && fin ? nullptr : S[j].acc,
-                                       c_acc, want_wp ? S[j].Xp : nullptr, c_wp, fin ? S[j].X : nullptr, c_fin));
-        }
-        return QF_OK;
-    };
-    for (int s = 0; s < steps; ++s) {
-        if (method == QF_ERK_EULER) {
-            QF_TRY(stage_all(true, 0.0, false, 0.0, true, dt));
-        } else if (method == QF_ERK_HEUN) {
-            QF_TRY(stage_all(true, 0.0, true, dt, false, 0.0));
-            QF_TRY(stage_all(false, 1.0, false, 0.0, true, dt / 2.0));
-        } else {
-            QF_TRY(stage_all(true, 0.0, true, dt / 2.0, false, 0.0));
-            QF_TRY(stage_all(false, 2.0, true, dt / 2.0, false, 0.0));
-            QF_TRY(stage_all(false, 2.0, true, dt, false, 0.0));
-            QF_TRY(stage_all(false, 1.0, false, 0.0, true, dt / 6.0));
-        }
-    }
-    for (int j = 0; j < k; ++j)
-        QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-    QF_HIP(hipStreamSynchronize(ctx->stream));
-    return QF_OK;
-}
 
 // ---- isomp_simple / isomp_quasinewton (quflow/integrators/isospectral.py:155-335) -----------
 // Both need X = A^-1 W and Wtilde = A^-1 (-X^H) with A = I - E, E = (stepsize/2) Ptilde
@@ -282,15 +144,7 @@ static int lu_hamiltonian(qf_ctx *ctx, ns_work &w, const cplx *Wt, double half_s
         return qf_launch_solve(ctx, ctx->poisson, Wt, w.E, half_stepsize, 0);
     }
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
-    if (ctx->hook_host_bytes < mbytes) {
-        for (int q = 0; q < 3; ++q) {
-            if (ctx->hook_host[q]) (void)hipHostFree(ctx->hook_host[q]);
-            ctx->hook_host[q] = nullptr;
-        }
-        ctx->hook_host_bytes = 0;
-        for (int q = 0; q < 3; ++q) QF_HIP(hipHostMalloc((void **)&ctx->hook_host[q], mbytes, hipHostMallocDefault));
-        ctx->hook_host_bytes = mbytes;
-    }
+    QF_TRY(qf_need_hook_host(ctx, 1));
     cplx *hW = ctx->hook_host[0], *hP = ctx->hook_host[1];
     QF_HIP(hipMemcpyAsync(hW, Wt, mbytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
@@ -323,11 +177,7 @@ static int isomp_simple_impl(qf_ctx *ctx, double dt, int steps, const qf_isomp_h
     QF_HIP(hipMemcpyAsync(Wt, ctx->W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));   // Wtilde = W.copy()
     ns_work w2;                                               // general branch: the inverse of Aalt = I + E
     if (general_branch) {
-        while (ctx->multi.size() < 2) {
-            cplx *p = nullptr;
-            QF_HIP(hipMalloc((void **)&p, mbytes));
-            ctx->multi.push_back(p);
-        }
+        QF_TRY(qf_need_matrices(ctx, ctx->multi, 2));
         w2.E = ctx->multi[0];        // -E
         w2.Y = ctx->multi[1];
         w2.R = w.R;
@@ -449,21 +299,10 @@ static int isomp_quasinewton_impl(qf_ctx *ctx, double dt, int steps, double tol,
 
 namespace {
 
-int stack_reserve(qf_ctx *ctx, size_t need)
-{
-    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
-    while (ctx->stack.size() < need) {
-        cplx *p = nullptr;
-        QF_HIP(hipMalloc((void **)&p, mbytes));
-        ctx->stack.push_back(p);
-    }
-    return QF_OK;
-}
-
 int stack_upload(qf_ctx *ctx, const void *states_host, int k)
 {
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
-    QF_TRY(stack_reserve(ctx, (size_t)5 * k));
+    QF_TRY(qf_need_matrices(ctx, ctx->stack, (size_t)5 * k));
     for (int j = 0; j < k; ++j)
         QF_HIP(hipMemcpyAsync(ctx->stack[5 * j], (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
     return QF_OK;
@@ -516,7 +355,7 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
     const double hb = qf_hbar(N);
     const double vareps = dt / (2 * hb);
     // per state: X, dX[2], Xhalf, PXc;  magnetic: Bhalf, BT, BTP
-    QF_TRY(stack_reserve(ctx, (size_t)5 * k + (magnetic ? 3 : 0)));
+    QF_TRY(qf_need_matrices(ctx, ctx->stack, (size_t)5 * k + (magnetic ? 3 : 0)));
     const int slots32 = (N + 31) / 32;
     if (!ctx->multi_rowpart) QF_HIP(hipMalloc((void **)&ctx->multi_rowpart, (size_t)2 * slots32 * N * sizeof(double)));   // (sized as hooks.hip sizes it)
     struct st { cplx *X, *dX[2], *Xhalf, *PXc; int cur; };
@@ -537,12 +376,7 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
 
     // the upper-triangle second product wants every state exactly skew-Hermitian
     bool tri = ctx->gemm_tri_allowed && ctx->sk_partial && N >= ctx->gemm_tri_min_n;
-    for (int j = 0; j < k && tri; ++j) {
-        QF_TRY(qf_launch_skew_defect(ctx, S[j].X, ctx->scalars + 4));
-        QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        QF_HIP(hipStreamSynchronize(ctx->stream));
-        tri = (ctx->host_scalars[0] == 0.0);
-    }
+    for (int j = 0; j < k && tri; ++j) QF_TRY(qf_exactly_skew(ctx, S[j].X, &tri));
     const bool tri_saved = ctx->gemm_tri, tri32_saved = ctx->gemm_tri32;
     ctx->gemm_tri = tri;
     ctx->gemm_tri32 = false;       // (stacks below N = 768 keep the full product)

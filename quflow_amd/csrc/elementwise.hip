@@ -143,7 +143,9 @@ __global__ __launch_bounds__(256) void k_update(int N, const C *__restrict__ PW,
 //   Wp   = W + c_wp*K                       next stage's argument (erk.py:142,146,150)
 //   Wout = W + c_fin*acc                    the update (erk.py:56,110,156)
 // SKEW: P and X skew-Hermitian => X@P = (P@X)^H, so B is the mirrored A tile (through LDS so
-// that both global reads are row-coalesced) and only one product is needed per stage.
+// that both global reads are row-coalesced) and only one product is needed per stage.  Only this
+// form is instantiated: with both products the flat k_erk_stage_forced below does the same
+// operations per element in the same order.
 template <bool SKEW>
 __global__ __launch_bounds__(256) void k_erk_stage(int N, const cplx *__restrict__ A, const cplx *__restrict__ B,
                                                     double inv_hb, const cplx *W, cplx *acc, double c_acc,
@@ -188,7 +190,35 @@ __global__ __launch_bounds__(256) void k_erk_stage(int N, const cplx *__restrict
     }
 }
 
-// out = a*X + b*Y + c*I  (Y may be nullptr; out may alias X or Y): the O(N^2) glue of the
+// The stage on both products, K = (A - B) * (1/hbar) + F (bracket(P, X) + forcing(P, X), erk.py:47-49; F == nullptr: no
+// force term), and the same running combinations: one entry per lane, grid-stride
+__global__ __launch_bounds__(256) void k_erk_stage_forced(size_t n, const cplx *__restrict__ A, const cplx *__restrict__ B,
+                                                           const cplx *__restrict__ F, double inv_hb, const cplx *W,
+                                                           cplx *acc, double c_acc, cplx *Wp, double c_wp, cplx *Wout,
+                                                           double c_fin)
+{
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        const cplx a = A[e], b = B[e];
+        double kr = (a.x - b.x) * inv_hb, ki = (a.y - b.y) * inv_hb;
+        if (F) {
+            const cplx f = F[e];
+            kr += f.x;
+            ki += f.y;
+        }
+        double ar = kr, ai = ki;
+        if (c_acc != 0.0) {
+            const cplx o = acc[e];
+            ar = o.x + c_acc * kr;
+            ai = o.y + c_acc * ki;
+        }
+        if (acc) acc[e] = make_double2(ar, ai);
+        const cplx w = W[e];
+        if (Wp) Wp[e] = make_double2(w.x + c_wp * kr, w.y + c_wp * ki);
+        if (Wout) Wout[e] = make_double2(w.x + c_fin * ar, w.y + c_fin * ai);
+    }
+}
+
+// out = a*X + b*Y + c*I (Y may be nullptr; out may alias X or Y): the O(N^2) glue of the
 // Newton-Schulz linear solves of isomp_simple / isomp_quasinewton (api_steppers.hip) and
 // Whalf = W + dW of a carried increment (api_isomp.hip)
 template <class C>
@@ -877,13 +907,23 @@ template <class C> int qf_launch_norm_inf(qf_ctx *ctx, const C *A, double *out_d
     return qf_launch_norm_from_rowpart(ctx, ctx->rowsum, 1, out_dev);
 }
 
-int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, double inv_hb, const cplx *W, cplx *acc,
+int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, const cplx *F, double inv_hb, const cplx *W, cplx *acc,
                         double c_acc, cplx *Wp, double c_wp, cplx *Wout, double c_fin)
 {
     const int N = ctx->N;
-    dim3 grid((N + TU - 1) / TU, (N + TU - 1) / TU), block(256);
-    if (B) hipLaunchKernelGGL(k_erk_stage<false>, grid, block, 0, ctx->stream, N, A, B, inv_hb, W, acc, c_acc, Wp, c_wp, Wout, c_fin);
-    else hipLaunchKernelGGL(k_erk_stage<true>, grid, block, 0, ctx->stream, N, A, B, inv_hb, W, acc, c_acc, Wp, c_wp, Wout, c_fin);
+    if (B) {
+        const size_t n = (size_t)N * N;
+        const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+        hipLaunchKernelGGL(k_erk_stage_forced, dim3(blocks), dim3(256), 0, ctx->stream, n, A, B, F, inv_hb, W, acc, c_acc, Wp, c_wp, Wout,
+                           c_fin);
+    } else {
+        if (F) {
+            qf_set_error("qf_launch_erk_stage: a force term needs both products");
+            return QF_ERR_INVALID;
+        }
+        dim3 grid((N + TU - 1) / TU, (N + TU - 1) / TU), block(256);
+        hipLaunchKernelGGL(k_erk_stage<true>, grid, block, 0, ctx->stream, N, A, B, inv_hb, W, acc, c_acc, Wp, c_wp, Wout, c_fin);
+    }
     QF_HIP(hipGetLastError());
     return QF_OK;
 }

@@ -1,5 +1,5 @@
-// isomp_fixedpoint and euler / heun / rk4 with HOST HOOKS (quflow/integrators/isospectral.py:338-613,
-// quflow/integrators/erk.py:19-160): `forcing(P, W[, time])`, a foreign `hamiltonian(W[, time])`,
+// isomp_fixedpoint with HOST HOOKS (quflow/integrators/isospectral.py:338-613): `forcing(P, W[, time])`, a foreign
+// `hamiltonian(W[, time])`,
 // `strang_splitting(h, W)`, `callback(W, dW)`, the general (not skew-Hermitian) branch of
 // select_skewherm(False), and all of these -- plus compsum -- on (k,N,N) stacks of states.
 //
@@ -22,7 +22,7 @@
 #include <limits>
 #include <vector>
 
-#include "qf_internal.h"
+#include "qf_api.h"
 
 #pragma clang fp contract(off)   // the reference's passes are separate numpy operations: no fused multiply-adds
 
@@ -174,34 +174,6 @@ __global__ __launch_bounds__(256) void k_hook_add_forcing(int N, const cplx *__r
     }
 }
 
-// K = (A - B) * (1/hbar) + F (bracket(P, X) + forcing(P, X), erk.py:47-49) and the running combinations
-// of qf_launch_erk_stage (elementwise.hip), for the hooked explicit steppers
-__global__ __launch_bounds__(256) void k_erk_stage_forced(size_t n, const cplx *__restrict__ A, const cplx *__restrict__ B,
-                                                           const cplx *__restrict__ F, double inv_hb, const cplx *W,
-                                                           cplx *acc, double c_acc, cplx *Wp, double c_wp, cplx *Wout,
-                                                           double c_fin)
-{
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const cplx a = A[e], b = B[e];
-        double kr = (a.x - b.x) * inv_hb, ki = (a.y - b.y) * inv_hb;
-        if (F) {
-            const cplx f = F[e];
-            kr += f.x;
-            ki += f.y;
-        }
-        double ar = kr, ai = ki;
-        if (c_acc != 0.0) {
-            const cplx o = acc[e];
-            ar = o.x + c_acc * kr;
-            ai = o.y + c_acc * ki;
-        }
-        if (acc) acc[e] = make_double2(ar, ai);
-        const cplx w = W[e];
-        if (Wp) Wp[e] = make_double2(w.x + c_wp * kr, w.y + c_wp * ki);
-        if (Wout) Wout[e] = make_double2(w.x + c_fin * ar, w.y + c_fin * ai);
-    }
-}
-
 // The installed affine forcing (qf_set_forcing), one pass, one entry per lane (16-byte loads and stores, consecutive lanes
 // on consecutive entries):
 //     p = Ph * pscale;  f = F0;  f += a_W X;  f += a_P p;  f += a_lap (Delta X);  out = s f
@@ -272,46 +244,6 @@ int launch_update(qf_ctx *ctx, const cplx *comm, const cplx *F, cplx *W, cplx *k
     if (kc) hipLaunchKernelGGL(k_hook_update<true>, dim3(blocks), dim3(256), 0, ctx->stream, n, comm, F, W, kc, dW, reinitialize, Whalf);
     else hipLaunchKernelGGL(k_hook_update<false>, dim3(blocks), dim3(256), 0, ctx->stream, n, comm, F, W, kc, dW, reinitialize, Whalf);
     QF_HIP(hipGetLastError());
-    return QF_OK;
-}
-
-int need_device(qf_ctx *ctx, size_t count)
-{
-    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
-    while (ctx->multi.size() < count) {
-        cplx *p = nullptr;
-        QF_HIP(hipMalloc((void **)&p, mbytes));
-        ctx->multi.push_back(p);
-    }
-    return QF_OK;
-}
-
-int need_host(qf_ctx *ctx, int k)
-{
-    const size_t bytes = (size_t)k * ctx->N * ctx->N * sizeof(cplx);
-    if (ctx->hook_host_bytes < bytes) {
-        for (int q = 0; q < 3; ++q) {
-            if (ctx->hook_host[q]) (void)hipHostFree(ctx->hook_host[q]);
-            ctx->hook_host[q] = nullptr;
-        }
-        ctx->hook_host_bytes = 0;
-        for (int q = 0; q < 3; ++q) QF_HIP(hipHostMalloc((void **)&ctx->hook_host[q], bytes, hipHostMallocDefault));
-        ctx->hook_host_bytes = bytes;
-    }
-    return QF_OK;
-}
-
-int hook_failed(const char *which, int rc)
-{
-    qf_set_error("%s hook returned %d", which, rc);
-    return QF_ERR_CALLBACK;
-}
-
-int read_scalar_sync(qf_ctx *ctx, const double *dev, double *out)
-{
-    QF_HIP(hipMemcpyAsync(ctx->host_scalars, dev, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    QF_HIP(hipStreamSynchronize(ctx->stream));
-    *out = ctx->host_scalars[0];
     return QF_OK;
 }
 
@@ -400,8 +332,8 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
         return QF_ERR_UNSUPPORTED;
     }
     const size_t per = 7;
-    QF_TRY(need_device(ctx, per * k + 4 + ((per_state || (states_p_open && k <= 48)) ? (size_t)k : 0)));
-    if (!resident) QF_TRY(need_host(ctx, k));
+    QF_TRY(qf_need_matrices(ctx, ctx->multi, per * k + 4 + ((per_state || (states_p_open && k <= 48)) ? (size_t)k : 0)));
+    if (!resident) QF_TRY(qf_need_hook_host(ctx, k));
     struct st { cplx *W, *dW[2], *Whalf, *PW, *F, *kc; int cur; };
     std::vector<st> S((size_t)k);
     for (int j = 0; j < k; ++j) {
@@ -426,7 +358,7 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
         if (!compsum) mach_eps = std::sqrt(mach_eps);
         double nrm = 0.0;
         QF_TRY(qf_launch_norm_inf(ctx, S[0].W, ctx->scalars));
-        QF_TRY(read_scalar_sync(ctx, ctx->scalars, &nrm));
+        QF_TRY(read_scalar(ctx, ctx->scalars, &nrm));
         tol = (mach_eps * dt / hb) * nrm;
     }
 
@@ -607,10 +539,10 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
                     }
                 } else {
                     QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + 1));
-                    QF_TRY(read_scalar_sync(ctx, ctx->scalars + 1, &resnorm));
+                    QF_TRY(read_scalar(ctx, ctx->scalars + 1, &resnorm));
                     if (magnetic && k > 1) {
                         double r1 = 0.0;
-                        QF_TRY(read_scalar_sync(ctx, ctx->scalars + 17, &r1));
+                        QF_TRY(read_scalar(ctx, ctx->scalars + 17, &r1));
                         if (!QF_FINITE(r1)) resnorm = std::numeric_limits<double>::quiet_NaN();
                     }
                 }
@@ -684,200 +616,6 @@ int qf_isomp_forced(qf_ctx *ctx, double dt, int steps, double tol, int minit, in
     hooks.strang_table = strang_table;
     hooks.strang_key = strang_key;
     return hooked_body(ctx, nullptr, 1, dt, steps, tol, minit, maxit, 0, reinitialize, &hooks, stats_out);
-}
-
-// euler / heun / rk4 (quflow/integrators/erk.py:19-160) with `forcing(P, W)` and / or a foreign
-// `hamiltonian(W)`: the state and the stage combinations stay on the device; per right-hand side a
-// foreign Hamiltonian moves X down and P up, forcing moves P and X down (X only once) and F up.
-int qf_erk_hooked(qf_ctx *ctx, void *W_host, int method, double dt, int steps, const qf_isomp_hooks *hooks)
-{
-    if (!ctx) {
-        qf_set_error("null qf_ctx");
-        return QF_ERR_INVALID;
-    }
-    QF_HIP(hipSetDevice(ctx->device));
-    if (!W_host || !hooks || method < QF_ERK_EULER || method > QF_ERK_RK4 || steps < 0) {
-        qf_set_error("qf_erk_hooked: bad arguments (method=%d, steps=%d)", method, steps);
-        return QF_ERR_INVALID;
-    }
-    if (ctx->forcing_on && hooks->forcing) {
-        qf_set_error("qf_erk_hooked: a forcing is installed on this context (qf_set_forcing) and a `forcing` hook is given as well");
-        return QF_ERR_UNSUPPORTED;
-    }
-    if (ctx->forcing_on && ctx->stoch.on) {
-        qf_set_error("qf_erk_hooked: a stochastic forcing is installed (qf_set_stochastic_forcing): noise inside Runge-Kutta "
-                     "stages is not defined here; qf_isomp_forced and qf_isomp_hooked (k = 1) follow it");
-        return QF_ERR_UNSUPPORTED;
-    }
-    const bool dev_forced = ctx->forcing_on;       // the installed forcing: formed on the device, unscaled as the hook's is
-    const int N = ctx->N;
-    const size_t NN = (size_t)N * N, mbytes = NN * sizeof(cplx);
-    const double inv_hb = 1.0 / qf_hbar(N);
-    QF_TRY(need_host(ctx, 1));
-    QF_TRY(need_device(ctx, 1));
-    ctx->w_skew_known = false;
-    cplx *W = ctx->W, *Wp = ctx->Whalf, *P = ctx->Phalf, *A = ctx->PW, *B = ctx->stage, *acc = ctx->dW[0], *F = ctx->multi[0];
-    cplx *hX = ctx->hook_host[0], *hP = ctx->hook_host[1], *hF = ctx->hook_host[2];
-    QF_HIP(hipMemcpyAsync(W, W_host, mbytes, hipMemcpyHostToDevice, ctx->stream));
-    const unsigned blocks = (unsigned)((NN + 255) / 256 < 4096 ? (NN + 255) / 256 : 4096);
-    // products and forcing of one right-hand side rhs(P, X) at X (a device matrix)
-    auto rhs = [&](const cplx *X) -> int {
-        bool have_x = false;
-        if (hooks->hamiltonian) {
-            QF_HIP(hipMemcpyAsync(hX, X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-            QF_HIP(hipStreamSynchronize(ctx->stream));
-            have_x = true;
-            const int rc = hooks->hamiltonian(hooks->user, hX, hP, 0.0);
-            if (rc) return hook_failed("hamiltonian", rc);
-            QF_HIP(hipMemcpyAsync(P, hP, mbytes, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            QF_TRY(qf_launch_solve(ctx, ctx->poisson, X, P, 1.0, hooks->solve_skewh ? 1 : 0));
-        }
-        QF_TRY(qf_launch_zgemm(ctx, P, X, A, nullptr));      // bracket(P, X) = (P@X - X@P)/hbar, geometry.py:41-49
-        QF_TRY(qf_launch_zgemm(ctx, X, P, B, nullptr));
-        if (dev_forced) {
-            QF_TRY(qf_launch_forcing_affine(ctx, P, X, F, 1.0, 1.0));
-        } else if (hooks->forcing) {
-            if (!hooks->hamiltonian) QF_HIP(hipMemcpyAsync(hP, P, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-            if (!have_x) QF_HIP(hipMemcpyAsync(hX, X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-            QF_HIP(hipStreamSynchronize(ctx->stream));
-            const int rc = hooks->forcing(hooks->user, hP, hX, hF, 0.0);
-            if (rc) return hook_failed("forcing", rc);
-            QF_HIP(hipMemcpyAsync(F, hF, mbytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        return QF_OK;
-    };
-    const cplx *Fk = (hooks->forcing || dev_forced) ? F : nullptr;
-    auto stage = [&](cplx *acc_, double c_acc, cplx *Wp_, double c_wp, cplx *Wout_, double c_fin) -> int {
-        hipLaunchKernelGGL(k_erk_stage_forced, dim3(blocks), dim3(256), 0, ctx->stream, NN, A, B, Fk, inv_hb, W, acc_, c_acc, Wp_,
-                           c_wp, Wout_, c_fin);
-        QF_HIP(hipGetLastError());
-        return QF_OK;
-    };
-    for (int s = 0; s < steps; ++s) {
-        if (method == QF_ERK_EULER) {           // erk.py:53-56
-            QF_TRY(rhs(W));
-            QF_TRY(stage(nullptr, 0.0, nullptr, 0.0, W, dt));
-        } else if (method == QF_ERK_HEUN) {     // erk.py:101-110
-            QF_TRY(rhs(W));
-            QF_TRY(stage(acc, 0.0, Wp, dt, nullptr, 0.0));
-            QF_TRY(rhs(Wp));
-            QF_TRY(stage(acc, 1.0, nullptr, 0.0, W, dt / 2.0));
-        } else {                                // erk.py:146-156
-            QF_TRY(rhs(W));
-            QF_TRY(stage(acc, 0.0, Wp, dt / 2.0, nullptr, 0.0));
-            QF_TRY(rhs(Wp));
-            QF_TRY(stage(acc, 2.0, Wp, dt / 2.0, nullptr, 0.0));
-            QF_TRY(rhs(Wp));
-            QF_TRY(stage(acc, 2.0, Wp, dt, nullptr, 0.0));
-            QF_TRY(rhs(Wp));
-            QF_TRY(stage(acc, 1.0, nullptr, 0.0, W, dt / 6.0));
-        }
-    }
-    QF_HIP(hipMemcpyAsync(W_host, W, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-    QF_HIP(hipStreamSynchronize(ctx->stream));
-    return QF_OK;
-}
-
-// The same on a (k,N,N) stack of states (erk.py with batched input): `hamiltonian(stack)` returns ONE (N,N) stream
-// matrix (the built-in one solves for state 0, cpu.py:696-697), bracket(P, X_j) for every state, `forcing(P, stack)`
-// returns a stack.  States, stage arguments and accumulators stay on the device; per right-hand side a foreign
-// Hamiltonian moves the stage arguments down and P up, forcing moves P and the stage arguments down (once) and F up.
-int qf_erk_states_hooked(qf_ctx *ctx, void *states_host, int k, int method, double dt, int steps, const qf_isomp_hooks *hooks)
-{
-    if (!ctx) {
-        qf_set_error("null qf_ctx");
-        return QF_ERR_INVALID;
-    }
-    QF_HIP(hipSetDevice(ctx->device));
-    if (!states_host || !hooks || k < 1 || method < QF_ERK_EULER || method > QF_ERK_RK4 || steps < 0) {
-        qf_set_error("qf_erk_states_hooked: bad arguments (k=%d, method=%d, steps=%d)", k, method, steps);
-        return QF_ERR_INVALID;
-    }
-    QF_TRY(qf_refuse_forcing(ctx, "qf_erk_states_hooked"));
-    const int N = ctx->N;
-    const size_t NN = (size_t)N * N, mbytes = NN * sizeof(cplx);
-    const double inv_hb = 1.0 / qf_hbar(N);
-    QF_TRY(need_host(ctx, k));
-    QF_TRY(need_device(ctx, (size_t)5 * k));           // per state: X, stage argument, accumulator, forcing term, stream matrix
-    ctx->w_skew_known = false;
-    cplx *P = ctx->Phalf, *A = ctx->PW, *B = ctx->stage;
-    cplx *hX = ctx->hook_host[0], *hP = ctx->hook_host[1], *hF = ctx->hook_host[2];
-    auto X = [&](int j) { return ctx->multi[(size_t)5 * j]; };
-    auto Xp = [&](int j) { return ctx->multi[(size_t)5 * j + 1]; };
-    auto Acc = [&](int j) { return ctx->multi[(size_t)5 * j + 2]; };
-    auto F = [&](int j) { return ctx->multi[(size_t)5 * j + 3]; };
-    auto Pj = [&](int j) { return ctx->multi[(size_t)5 * j + 4]; };
-    // hooks->states_p: the foreign Hamiltonian fills one stream matrix PER STATE (bracket(P, W) batched, erk.py with a
-    // (k,N,N) P); otherwise one for all states
-    bool per_state = hooks->hamiltonian && hooks->states_p > 0;      // (< 0: settled by the hook's first call, as in qf_isomp_hooked)
-    bool states_p_open = hooks->hamiltonian && hooks->states_p < 0;
-    for (int j = 0; j < k; ++j)
-        QF_HIP(hipMemcpyAsync(X(j), (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
-    const unsigned blocks = (unsigned)((NN + 255) / 256 < 4096 ? (NN + 255) / 256 : 4096);
-    // one stage for the whole stack at the stage arguments (the states themselves when from_state)
-    auto stage_all = [&](bool from_state, double c_acc, bool want_wp, double c_wp, bool fin, double c_fin) -> int {
-        auto arg = [&](int j) { return from_state ? X(j) : Xp(j); };
-        bool have_x = false;
-        auto stack_down = [&]() -> int {
-            if (have_x) return QF_OK;
-            for (int j = 0; j < k; ++j) QF_HIP(hipMemcpyAsync(hX + (size_t)j * NN, arg(j), mbytes, hipMemcpyDeviceToHost, ctx->stream));
-            have_x = true;
-            return QF_OK;
-        };
-        if (hooks->hamiltonian) {
-            QF_TRY(stack_down());
-            QF_HIP(hipStreamSynchronize(ctx->stream));
-            const int rc = hooks->hamiltonian(hooks->user, hX, hP, 0.0);
-            if (rc) return hook_failed("hamiltonian", rc);
-            if (states_p_open) {
-                states_p_open = false;
-                per_state = hooks->states_p > 0;
-            }
-            if (per_state) {
-                for (int j = 0; j < k; ++j) QF_HIP(hipMemcpyAsync(Pj(j), hP + (size_t)j * NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                QF_HIP(hipMemcpyAsync(P, hP, mbytes, hipMemcpyHostToDevice, ctx->stream));
-            }
-        } else {
-            QF_TRY(qf_launch_solve(ctx, ctx->poisson, arg(0), P, 1.0, hooks->solve_skewh ? 1 : 0));
-        }
-        if (hooks->forcing) {
-            if (!hooks->hamiltonian) QF_HIP(hipMemcpyAsync(hP, P, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-            QF_TRY(stack_down());
-            QF_HIP(hipStreamSynchronize(ctx->stream));
-            const int rc = hooks->forcing(hooks->user, hP, hX, hF, 0.0);
-            if (rc) return hook_failed("forcing", rc);
-            for (int j = 0; j < k; ++j) QF_HIP(hipMemcpyAsync(F(j), hF + (size_t)j * NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-        for (int j = 0; j < k; ++j) {
-            const cplx *Pm = per_state ? Pj(j) : P;
-            QF_TRY(qf_launch_zgemm(ctx, Pm, arg(j), A, nullptr));      // bracket(P, X_j) = (P@X_j - X_j@P)/hbar, geometry.py:41-49
-            QF_TRY(qf_launch_zgemm(ctx, arg(j), Pm, B, nullptr));
-            hipLaunchKernelGGL(k_erk_stage_forced, dim3(blocks), dim3(256), 0, ctx->stream, NN, A, B, hooks->forcing ? F(j) : nullptr, inv_hb,
-                               X(j), (c_acc == 0.0 && !want_wp && fin) ? nullptr : Acc(j), c_acc, want_wp ? Xp(j) : nullptr, c_wp,
-                               fin ? X(j) : nullptr, c_fin);
-            QF_HIP(hipGetLastError());
-        }
-        return QF_OK;
-    };
-    for (int s = 0; s < steps; ++s) {
-        if (method == QF_ERK_EULER) {           // erk.py:53-56
-            QF_TRY(stage_all(true, 0.0, false, 0.0, true, dt));
-        } else if (method == QF_ERK_HEUN) {     // erk.py:101-110
-            QF_TRY(stage_all(true, 0.0, true, dt, false, 0.0));
-            QF_TRY(stage_all(false, 1.0, false, 0.0, true, dt / 2.0));
-        } else {                                // erk.py:146-156
-            QF_TRY(stage_all(true, 0.0, true, dt / 2.0, false, 0.0));
-            QF_TRY(stage_all(false, 2.0, true, dt / 2.0, false, 0.0));
-            QF_TRY(stage_all(false, 2.0, true, dt, false, 0.0));
-            QF_TRY(stage_all(false, 1.0, false, 0.0, true, dt / 6.0));
-        }
-    }
-    for (int j = 0; j < k; ++j)
-        QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, X(j), mbytes, hipMemcpyDeviceToHost, ctx->stream));
-    QF_HIP(hipStreamSynchronize(ctx->stream));
-    return QF_OK;
 }
 
 }  // extern "C"

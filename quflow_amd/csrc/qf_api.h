@@ -1,4 +1,4 @@
-// Shared by the five api_*.hip translation units (the C ABI of include/quflow_hip.h): the per-launch event scope,
+// Shared by the api_*.hip translation units (the C ABI of include/quflow_hip.h) and hooks.hip: the per-launch event scope,
 // small host helpers, and the few functions one unit defines and another calls.  Host code only.
 #pragma once
 
@@ -83,6 +83,50 @@ int read_scalar(qf_ctx *ctx, const double *dev, double *out)
     QF_HIP(hipStreamSynchronize(ctx->stream));
     *out = ctx->host_scalars[0];
     return QF_OK;
+}
+
+// *out = X is exactly skew-Hermitian (max_ij |X[i,j] + conj(X[j,i])| == 0): what lets a product stand for its mirror image
+int qf_exactly_skew(qf_ctx *ctx, const cplx *X, bool *out)
+{
+    QF_TRY(qf_launch_skew_defect(ctx, X, ctx->scalars + 4));
+    QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    *out = (ctx->host_scalars[0] == 0.0);
+    return QF_OK;
+}
+
+// `v` (ctx->multi or ctx->stack) holds at least `count` N x N device matrices: grown on demand, kept
+int qf_need_matrices(qf_ctx *ctx, std::vector<cplx *> &v, size_t count)
+{
+    const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
+    while (v.size() < count) {
+        cplx *p = nullptr;
+        QF_HIP(hipMalloc((void **)&p, mbytes));
+        v.push_back(p);
+    }
+    return QF_OK;
+}
+
+// the three pinned staging buffers of the host hooks hold k N x N matrices each
+int qf_need_hook_host(qf_ctx *ctx, int k)
+{
+    const size_t bytes = (size_t)k * ctx->N * ctx->N * sizeof(cplx);
+    if (ctx->hook_host_bytes < bytes) {
+        for (int q = 0; q < 3; ++q) {
+            if (ctx->hook_host[q]) (void)hipHostFree(ctx->hook_host[q]);
+            ctx->hook_host[q] = nullptr;
+        }
+        ctx->hook_host_bytes = 0;
+        for (int q = 0; q < 3; ++q) QF_HIP(hipHostMalloc((void **)&ctx->hook_host[q], bytes, hipHostMallocDefault));
+        ctx->hook_host_bytes = bytes;
+    }
+    return QF_OK;
+}
+
+int hook_failed(const char *which, int rc)
+{
+    qf_set_error("%s hook returned %d", which, rc);
+    return QF_ERR_CALLBACK;
 }
 
 }  // namespace

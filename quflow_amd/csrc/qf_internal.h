@@ -765,8 +765,9 @@ int qf_launch_inner(qf_ctx *ctx, const cplx *A, const cplx *B, double *out_dev);
 // the five sums of the MHD diagnostics in one pass over W, P = Delta^-1 W and Theta (part: 5 x 1024 doubles of block partials):
 // out_dev[0..4] = sum Re(W conj P), sum Re(Theta conj(Delta Theta)), sum Re(W conj Theta), sum |Theta|^2, sum |W|^2
 int qf_launch_mhd_sums(qf_ctx *ctx, const cplx *W, const cplx *P, const cplx *Theta, double *part, double *out_dev);
-// explicit Runge-Kutta stage on the products A = P@X, B = X@P (B == nullptr: B = A^H, skew-Hermitian case)
-int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, double inv_hb, const cplx *W, cplx *acc,
+// explicit Runge-Kutta stage on the products A = P@X, B = X@P and the force term F (nullptr: none).  B == nullptr: B = A^H,
+// the skew-Hermitian case on mirrored tiles (no force term there)
+int qf_launch_erk_stage(qf_ctx *ctx, const cplx *A, const cplx *B, const cplx *F, double inv_hb, const cplx *W, cplx *acc,
                         double c_acc, cplx *Wp, double c_wp, cplx *Wout, double c_fin);
 // magmp: magnetic terms into dW / Whalf + residual row sums (slots: ceil(N/32) column tiles of 32)
 int qf_launch_magnetic_fix(qf_ctx *ctx, const cplx *BTP, const cplx *BT, cplx *dW, const cplx *dW_old, const cplx *W,

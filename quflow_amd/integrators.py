@@ -829,74 +829,51 @@ def update_stats(stats, **kwargs):
             stats[arg] = val
 
 
-def _erk_hooked(method, W, dt, steps, hamiltonian, forcing, device):
-    """euler / heun / rk4 with `forcing(P, W)` or a foreign `hamiltonian(W)` (erk.py:47-56, 93-112,
-    142-160): qf_erk_hooked keeps the state and the stage combinations on the device and calls back."""
-    N = W.shape[-1]
-    Wc = np.ascontiguousarray(W, dtype=np.complex128)
-    table = _HookTable(N, 1, True)
-    aff = _installable_forcing(forcing, W)        # installed on the device for this call: no forcing hook
-    if forcing is not None and aff is None:
-        table.set_forcing(forcing, False)
-    if not _is_native_hamiltonian(hamiltonian):
-        table.set_hamiltonian(hamiltonian, False)
-    ctx = get_stepper_context(N, device)
-    with _forcing_on(ctx, aff):
-        rc = ctx._lib.qf_erk_hooked(ctx.handle, ptr(Wc), _lib.ERK_METHODS[method], float(dt), int(steps), ctypes.byref(table.c))
-    table.check(rc)
-    if Wc is not W:
-        W[...] = Wc
-    return W
-
-
 def _erk(method, W, dt, steps, hamiltonian, forcing, device=None):
+    """euler / heun / rk4 on one (N,N) state or a (k,N,N) stack (P from state 0, bracket(P, W) broadcast over the stack:
+    erk.py with (k,N,N) input).  With `forcing(P, W)` or a foreign `hamiltonian(W)` (erk.py:47-56, 93-112, 142-160) the
+    hooked entry points keep the states and the stage combinations on the device and call back."""
     _refuse_stochastic(forcing, method)       # (noise inside Runge-Kutta stages is not defined here)
     steps = _reference_args(W, steps)         # (erk.py: `for k in range(steps)`, in-place updates of W)
     if steps == 0 and not np.issubdtype(W.dtype, np.complexfloating):
         return W                 # the reference's empty loop never touches a real / integer W
     # a TridiagonalHamiltonian without `forcing` is installed for the call (with `forcing` it is the foreign callable)
     ham = _installable(hamiltonian, W) if forcing is None and _laplacian._SKEW_HERM_ and W.ndim in (2, 3) else None
-    if W.ndim == 3 and W.shape[1] == W.shape[2]:
-        # a stack of states: P from state 0, bracket(P, W) broadcast over the stack (erk.py with (k,N,N) input)
-        if forcing is not None or not (ham is not None or _is_native_hamiltonian(hamiltonian)):
-            if W.dtype != np.complex128:
-                raise NotImplementedError("forcing / foreign Hamiltonians need a complex128 state on the HIP path.")
-            # hooks see the whole stack; a foreign Hamiltonian returns ONE (N,N) stream matrix (qf_erk_states_hooked)
-            N, k = W.shape[-1], W.shape[0]
-            Wc = np.ascontiguousarray(W, dtype=np.complex128)
-            table = _HookTable(N, k, False)
-            if forcing is not None:
-                table.set_forcing(forcing, False)
-            if not _is_native_hamiltonian(hamiltonian):
-                # one stream matrix for all states or one per state: the first stage's evaluation tells
-                table.set_hamiltonian(hamiltonian, False, per_state=(None if k > 1 else False))
-            ctx = get_stepper_context(N, device)
-            table.check(ctx._lib.qf_erk_states_hooked(ctx.handle, ptr(Wc), int(k), _lib.ERK_METHODS[method], float(dt), int(steps),
-                                                      ctypes.byref(table.c)))
-            if Wc is not W:
-                W[...] = Wc
-            return W
-        ctx = get_context(W.shape[-1], device)
-        Wc = np.ascontiguousarray(W, dtype=np.complex128)
-        with _hamiltonian_on(ctx, ham):
-            _lib.check(ctx._lib.qf_erk_states(ctx.handle, ptr(Wc), int(W.shape[0]), _lib.ERK_METHODS[method], float(dt),
-                                              int(steps), int(_laplacian._SKEW_HERM_)))
-        if Wc is not W:
-            W[...] = Wc
-        return W
-    if W.ndim != 2 or W.shape[0] != W.shape[1]:
+    stacked = W.ndim == 3 and W.shape[1] == W.shape[2]
+    if not stacked and (W.ndim != 2 or W.shape[0] != W.shape[1]):
         raise ValueError("W must be a square matrix or a (k,N,N) stack")
-    if forcing is not None or not (ham is not None or _is_native_hamiltonian(hamiltonian)):
-        if W.dtype != np.complex128:
-            raise NotImplementedError("forcing / foreign Hamiltonians need a complex128 state on the HIP path.")
-        return _erk_hooked(method, W, dt, steps, hamiltonian, forcing, device)
-    ctx = get_context(W.shape[-1], device)
+    foreign = not (ham is not None or _is_native_hamiltonian(hamiltonian))
+    hooked = forcing is not None or foreign
+    if hooked and W.dtype != np.complex128:
+        raise NotImplementedError("forcing / foreign Hamiltonians need a complex128 state on the HIP path.")
+    N, k = W.shape[-1], (W.shape[0] if stacked else 1)
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
-    with _hamiltonian_on(ctx, ham):
-        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-        _lib.check(ctx._lib.qf_erk(ctx.handle, _lib.ERK_METHODS[method], float(dt), int(steps),
-                                   int(_laplacian._SKEW_HERM_)))
-        _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
+    call = (_lib.ERK_METHODS[method], float(dt), int(steps))
+    if hooked:
+        # hooks see the whole stack; a foreign Hamiltonian returns one stream matrix for all states or one per state: the
+        # first stage's evaluation tells.  An AffineForcing on one (N,N) state is installed on the device: no forcing hook
+        table = _HookTable(N, k, not stacked)
+        aff = _installable_forcing(forcing, W)
+        if forcing is not None and aff is None:
+            table.set_forcing(forcing, False)
+        if not _is_native_hamiltonian(hamiltonian):
+            table.set_hamiltonian(hamiltonian, False, per_state=(None if k > 1 else False))
+        ctx = get_stepper_context(N, device)
+        with _forcing_on(ctx, aff):
+            if stacked:
+                rc = ctx._lib.qf_erk_states_hooked(ctx.handle, ptr(Wc), int(k), *call, ctypes.byref(table.c))
+            else:
+                rc = ctx._lib.qf_erk_hooked(ctx.handle, ptr(Wc), *call, ctypes.byref(table.c))
+        table.check(rc)
+    else:
+        ctx = get_context(N, device)
+        with _hamiltonian_on(ctx, ham):
+            if stacked:
+                _lib.check(ctx._lib.qf_erk_states(ctx.handle, ptr(Wc), int(k), *call, int(_laplacian._SKEW_HERM_)))
+            else:
+                _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+                _lib.check(ctx._lib.qf_erk(ctx.handle, *call, int(_laplacian._SKEW_HERM_)))
+                _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     if Wc is not W:
         W[...] = Wc                  # in-place contract (erk.py:56,110,156)
     return W
