@@ -666,12 +666,7 @@ template <class S> int fused_leave(qf_ctx *ctx, int steps, qf_isomp_stats *stats
         qf_set_error("qf_isomp: a device-side wait of the second product ran out (a parked partial tile or a mirrored result tile was never published)");
         return QF_ERR_STATE;
     }
-    if (stats_out) {
-        stats_out->total_iterations = steps > 0 ? rec->total_iterations : 0;
-        stats_out->number_of_maxit = steps > 0 ? rec->number_of_maxit : 0;
-        stats_out->tol_used = rec->tol;
-        stats_out->last_resnorm = rec->resnorm;
-    }
+    fill_stats(stats_out, steps > 0 ? rec->total_iterations : 0, steps > 0 ? rec->number_of_maxit : 0, rec->tol, rec->resnorm);
     return QF_OK;
 }
 
@@ -699,14 +694,7 @@ int isomp_impl(qf_ctx *ctx, double dt, int steps, double tol, int minit, int max
                qf_isomp_stats *stats_out, bool carry_increment)
 {
     QF_TRY(check_ctx(ctx));
-    if (minit < 1) {  // isospectral.py:400
-        qf_set_error("minit must be at least 1.");
-        return QF_ERR_INVALID;
-    }
-    if (maxit < minit) {  // isospectral.py:401
-        qf_set_error("maxit must be at minit.");
-        return QF_ERR_INVALID;
-    }
+    QF_TRY(check_iteration_args(minit, maxit));
     if (steps < 0) {
         qf_set_error("qf_isomp: steps must be >= 0");
         return QF_ERR_INVALID;
@@ -859,12 +847,7 @@ int isomp_impl(qf_ctx *ctx, double dt, int steps, double tol, int minit, int max
         qf_set_error("qf_isomp: a device-side wait of the second product ran out (a parked partial tile or a mirrored result tile was never published)");
         return QF_ERR_STATE;
     }
-    if (stats_out) {
-        stats_out->total_iterations = st.total_iterations;
-        stats_out->number_of_maxit = st.number_of_maxit;
-        stats_out->tol_used = tol;
-        stats_out->last_resnorm = rec->resnorm;
-    }
+    fill_stats(stats_out, st.total_iterations, st.number_of_maxit, tol, rec->resnorm);
     return QF_OK;
 }
 
@@ -881,14 +864,7 @@ int isomp_multi(qf_ctx **ctxs, int k, double dt, int steps, double tol, int mini
         qf_set_error("%s: bad arguments (k=%d)", name, k);
         return QF_ERR_INVALID;
     }
-    if (minit < 1) {
-        qf_set_error("minit must be at least 1.");
-        return QF_ERR_INVALID;
-    }
-    if (maxit < minit) {
-        qf_set_error("maxit must be at minit.");
-        return QF_ERR_INVALID;
-    }
+    QF_TRY(check_iteration_args(minit, maxit));
     if (steps < 0) {
         qf_set_error("%s: steps must be >= 0", name);
         return QF_ERR_INVALID;

@@ -276,12 +276,7 @@ static int isomp_quasinewton_impl(qf_ctx *ctx, double dt, int steps, double tol,
     }
     // leave Wtilde where later calls expect scratch only; nothing to restore
     QF_HIP(hipStreamSynchronize(ctx->stream));
-    if (stats_out) {
-        stats_out->total_iterations = total_iterations;
-        stats_out->number_of_maxit = number_of_maxit;
-        stats_out->tol_used = tol;
-        stats_out->last_resnorm = resnorm;
-    }
+    fill_stats(stats_out, total_iterations, number_of_maxit, tol, resnorm);
     return QF_OK;
 }
 
@@ -331,19 +326,6 @@ void mhd_from_sums(const qf_ctx *ctx, double out[5])
     out[4] = (h[4] / N) / 2.0;       // S  = <W, W>/2
 }
 
-int states_check_args(int minit, int maxit)
-{
-    if (minit < 1) {
-        qf_set_error("minit must be at least 1.");
-        return QF_ERR_INVALID;
-    }
-    if (maxit < minit) {
-        qf_set_error("maxit must be at minit.");
-        return QF_ERR_INVALID;
-    }
-    return QF_OK;
-}
-
 // `steps` steps of the k states in ctx->stack[5 j]: dX restarts from zero, the exit test is state 0's, the finite check covers
 // every state.  states_host != nullptr: the result is downloaded there;  mhd_out != nullptr (magnetic): the diagnostics of
 // the new state -- either one under the closing synchronisation.
@@ -377,23 +359,17 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
     // the upper-triangle second product wants every state exactly skew-Hermitian
     bool tri = ctx->gemm_tri_allowed && ctx->sk_partial && N >= ctx->gemm_tri_min_n;
     for (int j = 0; j < k && tri; ++j) QF_TRY(qf_exactly_skew(ctx, S[j].X, &tri));
-    const bool tri_saved = ctx->gemm_tri, tri32_saved = ctx->gemm_tri32;
+    // (the context's own selection comes back however the loop is left)
+    struct tri_guard {
+        qf_ctx *ctx;
+        bool tri, tri32;
+        ~tri_guard() { ctx->gemm_tri = tri; ctx->gemm_tri32 = tri32; }
+    } guard{ctx, ctx->gemm_tri, ctx->gemm_tri32};
     ctx->gemm_tri = tri;
     ctx->gemm_tri32 = false;       // (stacks below N = 768 keep the full product)
-    auto restore = [&](int rc) { ctx->gemm_tri = tri_saved; ctx->gemm_tri32 = tri32_saved; return rc; };
-#define QF_TRY_R(call)                  \
-    do {                                \
-        int _r = (call);                \
-        if (_r != QF_OK) return restore(_r); \
-    } while (0)
 
     // tolerance from state 0 (isospectral.py:440-452; magmp uses sqrt(eps) always, mhd.py:331-341)
-    if (tol < 0) {
-        double nrm = 0.0;
-        QF_TRY_R(qf_launch_norm_inf(ctx, S[0].X, ctx->scalars));
-        QF_TRY_R(read_scalar(ctx, ctx->scalars, &nrm));
-        tol = (std::sqrt(std::numeric_limits<double>::epsilon()) * dt / hb) * nrm;
-    }
+    if (tol < 0) QF_TRY(auto_tolerance(ctx, S[0].X, std::sqrt(std::numeric_limits<double>::epsilon()) * dt / hb, &tol));
 
     long long total_iterations = 0, number_of_maxit = 0;
     double resnorm = 0.0;
@@ -404,16 +380,16 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
             total_iterations += 1;
             // Phalf = vareps * Delta^-1 Whalf[0]   (+ Bhalf = vareps * Delta Thetahalf)
             // (magmp's Hamiltonian is solve_mhd: Poisson as such; a stack of isomp states follows the flow's)
-            if (magnetic) QF_TRY_R(qf_launch_solve(ctx, ctx->poisson, S[0].Xhalf, ctx->Phalf, vareps, 1));
-            else QF_TRY_R(qf_launch_hamiltonian(ctx, S[0].Xhalf, ctx->Phalf, vareps));
+            if (magnetic) QF_TRY(qf_launch_solve(ctx, ctx->poisson, S[0].Xhalf, ctx->Phalf, vareps, 1));
+            else QF_TRY(qf_launch_hamiltonian(ctx, S[0].Xhalf, ctx->Phalf, vareps));
             if (magnetic) {
-                QF_TRY_R(qf_launch_laplace_scaled(ctx, S[1].Xhalf, Bhalf, vareps));      // (one launch, the bits of laplace + lincomb)
+                QF_TRY(qf_launch_laplace_scaled(ctx, S[1].Xhalf, Bhalf, vareps));      // (one launch, the bits of laplace + lincomb)
             }
             for (int j = 0; j < k; ++j)                                   // Pstatecomm = Phalf @ statehalf
-                QF_TRY_R(qf_launch_zgemm(ctx, ctx->Phalf, S[j].Xhalf, S[j].PXc, nullptr));
+                QF_TRY(qf_launch_zgemm(ctx, ctx->Phalf, S[j].Xhalf, S[j].PXc, nullptr));
             if (magnetic) {
-                QF_TRY_R(qf_launch_zgemm(ctx, Bhalf, S[1].Xhalf, BT, nullptr));       // BThetacomm
-                QF_TRY_R(qf_launch_zgemm(ctx, BT, ctx->Phalf, BTP, nullptr));         // BThetaPhalf
+                QF_TRY(qf_launch_zgemm(ctx, Bhalf, S[1].Xhalf, BT, nullptr));       // BThetacomm
+                QF_TRY(qf_launch_zgemm(ctx, BT, ctx->Phalf, BTP, nullptr));         // BThetaPhalf
             }
             for (int j = 0; j < k; ++j) {
                 // dX = PXc @ Phalf + (PXc - PXc^H);  Xhalf = X + dX;  row sums of |dX_old - dX|
@@ -424,47 +400,29 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
                 ep.dW[1] = S[j].dX[S[j].cur ^ 1];
                 ep.Whalf = S[j].Xhalf;
                 ep.rowpart = ctx->rowpart;
-                QF_TRY_R(qf_launch_zgemm(ctx, S[j].PXc, ctx->Phalf, nullptr, &ep));
+                QF_TRY(qf_launch_zgemm(ctx, S[j].PXc, ctx->Phalf, nullptr, &ep));
                 if (j == 0) {
                     if (magnetic) {
-                        QF_TRY_R(qf_launch_magnetic_fix(ctx, BTP, BT, S[0].dX[S[0].cur ^ 1], S[0].dX[S[0].cur], S[0].X,
-                                                        S[0].Xhalf, ctx->multi_rowpart));
-                        QF_TRY_R(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots32, ctx->scalars + 1));
+                        QF_TRY(qf_launch_magnetic_fix(ctx, BTP, BT, S[0].dX[S[0].cur ^ 1], S[0].dX[S[0].cur], S[0].X,
+                                                      S[0].Xhalf, ctx->multi_rowpart));
+                        QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots32, ctx->scalars + 16));
                     } else {
-                        QF_TRY_R(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + 1));
+                        QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + 16));
                     }
                 } else if (i + 1 >= minit) {
                     // the exit test looks at state 0's residual, but scipy.linalg.norm checks the WHOLE stack for infs / NaNs
                     // before it reduces (check_finite, isospectral.py:528): the other states' norms are formed for that check --
-                    // 48 result slots, the states beyond them folded on the device into scalars[8] (through scalars[9])
-                    QF_TRY_R(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + (j < 48 ? 16 + j : 9)));
-                    if (j == 48 && hipMemsetAsync(ctx->scalars + 8, 0, sizeof(double), ctx->stream) != hipSuccess) {
-                        qf_set_error("qf_isomp_states: clearing the folded finite flag failed");
-                        return restore(QF_ERR_HIP);
-                    }
-                    if (j >= 48) QF_TRY_R(qf_launch_fold_nonfinite(ctx, ctx->scalars + 9, ctx->scalars + 8));
+                    // the slots of read_stack_resnorm, the states beyond 48 folded on the device into scalars[8]
+                    QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->rowpart, qf_rowpart_slots(ctx), ctx->scalars + (j < 48 ? 16 + j : 9)));
+                    if (j == 48) QF_HIP(hipMemsetAsync(ctx->scalars + 8, 0, sizeof(double), ctx->stream));
+                    if (j >= 48) QF_TRY(qf_launch_fold_nonfinite(ctx, ctx->scalars + 9, ctx->scalars + 8));
                 }
                 S[j].cur ^= 1;
             }
             if (i + 1 >= minit) {
                 const double resnorm_old = resnorm;
-                const int kk = k < 48 ? k : 48;
-                if (kk > 1 && hipMemcpyAsync(ctx->host_scalars + 1, ctx->scalars + 17, (size_t)(kk - 1) * sizeof(double), hipMemcpyDeviceToHost,
-                                             ctx->stream) != hipSuccess) {
-                    qf_set_error("qf_isomp_states: copy of the states' residual norms failed");
-                    return restore(QF_ERR_HIP);
-                }
-                if (k > 48 && hipMemcpyAsync(ctx->host_scalars + 48, ctx->scalars + 8, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-                    qf_set_error("qf_isomp_states: copy of the folded finite flag failed");
-                    return restore(QF_ERR_HIP);
-                }
-                QF_TRY_R(read_scalar(ctx, ctx->scalars + 1, &resnorm));
-                bool finite = QF_FINITE(resnorm) && (k <= 48 || QF_FINITE(ctx->host_scalars[48]));
-                for (int j = 1; j < kk; ++j) finite = finite && QF_FINITE(ctx->host_scalars[j]);
-                if (!finite) {       // scipy.linalg.norm raises here (isospectral.py:534, mhd.py: same test)
-                    qf_set_error("array must not contain infs or NaNs");
-                    return restore(QF_ERR_NONFINITE);
-                }
+                // (scipy.linalg.norm raises for a non-finite state here: isospectral.py:534, mhd.py: same test)
+                QF_TRY(read_stack_resnorm(ctx, k, false, &resnorm));
                 if (resnorm <= tol || resnorm >= resnorm_old) {
                     broke = true;
                     break;
@@ -474,14 +432,11 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
         if (!broke) number_of_maxit += 1;
         // W += 2 (PXc - PXc^H) for every state; Xhalf = X + dX for the next step
         for (int j = 0; j < k; ++j)
-            QF_TRY_R(qf_launch_update(ctx, S[j].PXc, S[j].X, S[j].dX[S[j].cur], S[j].dX[S[j].cur], S[j].Xhalf, nullptr,
-                                      reinitialize));
+            QF_TRY(qf_launch_update(ctx, S[j].PXc, S[j].X, S[j].dX[S[j].cur], S[j].dX[S[j].cur], S[j].Xhalf, nullptr,
+                                    reinitialize));
         if (magnetic)
-            QF_TRY_R(qf_launch_magnetic_update(ctx, BT, S[0].X, reinitialize ? nullptr : S[0].dX[S[0].cur], S[0].Xhalf));
+            QF_TRY(qf_launch_magnetic_update(ctx, BT, S[0].X, reinitialize ? nullptr : S[0].dX[S[0].cur], S[0].Xhalf));
     }
-#undef QF_TRY_R
-    ctx->gemm_tri = tri_saved;
-    ctx->gemm_tri32 = tri32_saved;
     // what the caller queues behind the last step rides on the call's closing synchronisation: the MHD diagnostics
     // (qf_states_advance_diag) or the download (qf_isomp_states)
     if (mhd_out) QF_TRY(enqueue_mhd_diagnostics(ctx));
@@ -490,15 +445,9 @@ int states_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
             QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].X, mbytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     if (mhd_out) mhd_from_sums(ctx, mhd_out);
-    if (stats_out) {
-        stats_out->total_iterations = total_iterations;
-        stats_out->number_of_maxit = number_of_maxit;
-        stats_out->tol_used = tol;
-        stats_out->last_resnorm = resnorm;
-    }
+    fill_stats(stats_out, total_iterations, number_of_maxit, tol, resnorm);
     return QF_OK;
 }
-
 
 }  // namespace
 
@@ -508,7 +457,7 @@ int qf_isomp_states(qf_ctx *ctx, void *states_host, int k, double dt, int steps,
                     int reinitialize, int magnetic, qf_isomp_stats *stats_out)
 {
     QF_TRY(check_ctx(ctx));
-    QF_TRY(states_check_args(minit, maxit));
+    QF_TRY(check_iteration_args(minit, maxit));
     if (!states_host || k < 1 || steps < 0 || (magnetic && k != 2)) {
         qf_set_error("qf_isomp_states: bad arguments (k=%d, steps=%d, magnetic=%d)", k, steps, magnetic);
         return QF_ERR_INVALID;
@@ -562,7 +511,7 @@ int qf_states_advance_diag(qf_ctx *ctx, double dt, int steps, double tol, int mi
                            qf_isomp_stats *stats_out, double *mhd_out)
 {
     QF_TRY(check_ctx(ctx));
-    QF_TRY(states_check_args(minit, maxit));
+    QF_TRY(check_iteration_args(minit, maxit));
     QF_TRY(need_stack(ctx, "qf_states_advance"));
     if (steps < 0 || (magnetic && ctx->stack_k != 2) || (mhd_out && !magnetic)) {
         qf_set_error("qf_states_advance: bad arguments (resident k=%d, steps=%d, magnetic=%d)", ctx->stack_k, steps, magnetic);

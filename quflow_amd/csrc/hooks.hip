@@ -270,108 +270,125 @@ int qf_launch_forcing_affine(qf_ctx *ctx, const cplx *Ph, const cplx *X, cplx *o
 
 namespace {
 
-// The loop of qf_isomp_hooked and of qf_isomp_forced, written once.  states_host != nullptr: the (k,N,N) state comes from
-// the host and goes back there;  nullptr (k == 1): it is taken from the context's resident state ctx->W and returned to it
-// by device copies -- no N^2 transfer in either direction, no pinned staging.
-int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
-                int compsum, int reinitialize, const qf_isomp_hooks *hooks, qf_isomp_stats *stats_out)
-{
-    if (!ctx) {
-        qf_set_error("null qf_ctx");
-        return QF_ERR_INVALID;
-    }
-    QF_HIP(hipSetDevice(ctx->device));
-    if (minit < 1) {  // isospectral.py:400
-        qf_set_error("minit must be at least 1.");
-        return QF_ERR_INVALID;
-    }
-    if (maxit < minit) {  // isospectral.py:401
-        qf_set_error("maxit must be at minit.");
-        return QF_ERR_INVALID;
-    }
-    const bool resident = states_host == nullptr;
-    if (!hooks || k < 1 || steps < 0 || (resident && k != 1)) {
-        qf_set_error("qf_isomp_hooked: bad arguments (k=%d, steps=%d)", k, steps);
-        return QF_ERR_INVALID;
-    }
-    // an installed forcing (qf_set_forcing) is applied on the device where the host hook is absent: one (N,N) state, not magmp
-    if (ctx->forcing_on && (k > 1 || hooks->magnetic)) return qf_refuse_forcing(ctx, k > 1 ? "qf_isomp_hooked on a stack" : "qf_isomp_hooked (magmp)");
-    if (ctx->forcing_on && hooks->forcing) {
-        qf_set_error("qf_isomp_hooked: a forcing is installed on this context (qf_set_forcing) and a `forcing` hook is given as well");
-        return QF_ERR_UNSUPPORTED;
-    }
-    const bool dev_forced = ctx->forcing_on;
-    if (compsum && (hooks->forcing || dev_forced) && steps > 0) {   // isospectral.py:588-589
-        qf_set_error("Compensated sum with forcing is not yet implemented.");
-        return QF_ERR_UNSUPPORTED;
-    }
-    const int N = ctx->N;
-    const size_t NN = (size_t)N * N, mbytes = NN * sizeof(cplx);
-    const double hb = qf_hbar(N);                 // isospectral.py:436
-    const double vareps = dt / (2 * hb);          // isospectral.py:437
-    const bool magnetic = hooks->magnetic != 0;
-    if (magnetic && (k != 2 || compsum || !hooks->skewh || hooks->strang || hooks->strang_table)) {
-        qf_set_error("qf_isomp_hooked: magmp (mhd.py:235-456) takes a (2,N,N) state, skew-Hermitian matrices, no compsum, no strang_splitting");
-        return QF_ERR_INVALID;
-    }
-    const bool skew = hooks->skewh != 0;
-    const bool forced = hooks->forcing != nullptr || dev_forced;
-    const bool foreign = hooks->hamiltonian != nullptr;
-    ctx->w_skew_known = false;
-    ctx->increment_valid = false;
+// The loop of qf_isomp_hooked and of qf_isomp_forced, written once: what its stages share, and the stages in the order
+// hooked_body runs them.  states_host != nullptr: the (k,N,N) state comes from the host and goes back there;  nullptr
+// (k == 1): it is taken from the context's resident state ctx->W and returned to it by device copies -- no N^2 transfer in
+// either direction, no pinned staging.
+struct hooked_loop {
+    qf_ctx *ctx;
+    void *states_host;
+    int k;
+    double dt, tol;
+    int compsum, reinitialize;
+    const qf_isomp_hooks *hooks;
 
     // per state: W, dW[2], Whalf, PW (-> comm), F, Kahan term; shared: C3 (general branch), magmp: Bhalf, BT, BTP
-    // states_p: the foreign Hamiltonian returns one stream matrix PER STATE ((k,N,N): np.matmul batches the products)
-    // states_p < 0: the caller does not know yet -- the hook stores 0 or 1 into the field during its FIRST call and the
-    // answer is read back behind that call (no entry probe: the user's function is evaluated as often as the reference
-    // evaluates it); the k stream matrices are reserved up front while that is open
-    bool per_state = foreign && hooks->states_p > 0 && !magnetic && k > 1;
-    bool states_p_open = foreign && hooks->states_p < 0 && !magnetic && k > 1;
-    if (per_state && k > 48) {
+    static constexpr size_t per = 7;
+    struct st { cplx *W, *dW[2], *Whalf, *PW, *F, *kc; int cur; };
+    std::vector<st> S;
+    bool resident = false, dev_forced = false, magnetic = false, skew = false, forced = false, foreign = false;
+    bool per_state = false, states_p_open = false;
+    int N = 0, slots = 0;
+    size_t NN = 0, mbytes = 0;
+    double vareps = 0.0, time = 0.0;
+    cplx *C3 = nullptr, *Bhalf = nullptr, *BT = nullptr, *BTP = nullptr, *hW = nullptr, *hP = nullptr, *hF = nullptr;
+
+    cplx *Pj(int j) const { return per_state ? ctx->multi[per * k + 4 + j] : ctx->Phalf; }     // state j's Phalf
+
+    int too_many_stream_matrices() const
+    {
         qf_set_error("qf_isomp_hooked: a Hamiltonian with one stream matrix per state takes at most 48 states (k=%d)", k);
         return QF_ERR_UNSUPPORTED;
     }
-    const size_t per = 7;
-    QF_TRY(qf_need_matrices(ctx, ctx->multi, per * k + 4 + ((per_state || (states_p_open && k <= 48)) ? (size_t)k : 0)));
-    if (!resident) QF_TRY(qf_need_hook_host(ctx, k));
-    struct st { cplx *W, *dW[2], *Whalf, *PW, *F, *kc; int cur; };
-    std::vector<st> S((size_t)k);
-    for (int j = 0; j < k; ++j) {
-        cplx **b = &ctx->multi[per * j];
-        S[j] = {b[0], {b[1], b[2]}, b[3], b[4], b[5], b[6], 0};
-        if (resident) QF_HIP(hipMemcpyAsync(S[j].W, ctx->W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
-        else QF_HIP(hipMemcpyAsync(S[j].W, (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
-        QF_HIP(hipMemsetAsync(S[j].dW[0], 0, mbytes, ctx->stream));                      // dW = zeros_like(W), :430
-        QF_HIP(hipMemcpyAsync(S[j].Whalf, S[j].W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (compsum) QF_HIP(hipMemsetAsync(S[j].kc, 0, mbytes, ctx->stream));             // :457
-    }
-    auto Pj = [&](int j) { return per_state ? ctx->multi[per * k + 4 + j] : ctx->Phalf; };     // state j's Phalf
-    cplx *C3 = ctx->multi[per * k];
-    cplx *Bhalf = ctx->multi[per * k + 1], *BT = ctx->multi[per * k + 2], *BTP = ctx->multi[per * k + 3];
-    cplx *hW = ctx->hook_host[0], *hP = ctx->hook_host[1], *hF = ctx->hook_host[2];
-    const int slots = (N + TH - 1) / TH;
-    if (!ctx->multi_rowpart) QF_HIP(hipMalloc((void **)&ctx->multi_rowpart, (size_t)2 * slots * N * sizeof(double)));   // (second half: magmp's second state, finite check)
 
-    // tolerance from state 0 (isospectral.py:440-452)
-    if (tol < 0) {
-        double mach_eps = std::numeric_limits<double>::epsilon();
-        if (!compsum) mach_eps = std::sqrt(mach_eps);
-        double nrm = 0.0;
-        QF_TRY(qf_launch_norm_inf(ctx, S[0].W, ctx->scalars));
-        QF_TRY(read_scalar(ctx, ctx->scalars, &nrm));
-        tol = (mach_eps * dt / hb) * nrm;
+    // ---- set-up, first half: what the call may be asked, and what kind of run it is
+    int setup(int steps)
+    {
+        resident = states_host == nullptr;
+        if (!hooks || k < 1 || steps < 0 || (resident && k != 1)) {
+            qf_set_error("qf_isomp_hooked: bad arguments (k=%d, steps=%d)", k, steps);
+            return QF_ERR_INVALID;
+        }
+        // an installed forcing (qf_set_forcing) is applied on the device where the host hook is absent: one (N,N) state, not magmp
+        if (ctx->forcing_on && (k > 1 || hooks->magnetic)) return qf_refuse_forcing(ctx, k > 1 ? "qf_isomp_hooked on a stack" : "qf_isomp_hooked (magmp)");
+        if (ctx->forcing_on && hooks->forcing) {
+            qf_set_error("qf_isomp_hooked: a forcing is installed on this context (qf_set_forcing) and a `forcing` hook is given as well");
+            return QF_ERR_UNSUPPORTED;
+        }
+        dev_forced = ctx->forcing_on;
+        if (compsum && (hooks->forcing || dev_forced) && steps > 0) {   // isospectral.py:588-589
+            qf_set_error("Compensated sum with forcing is not yet implemented.");
+            return QF_ERR_UNSUPPORTED;
+        }
+        N = ctx->N;
+        NN = (size_t)N * N;
+        mbytes = NN * sizeof(cplx);
+        vareps = dt / (2 * qf_hbar(N));           // isospectral.py:436-437
+        magnetic = hooks->magnetic != 0;
+        if (magnetic && (k != 2 || compsum || !hooks->skewh || hooks->strang || hooks->strang_table)) {
+            qf_set_error("qf_isomp_hooked: magmp (mhd.py:235-456) takes a (2,N,N) state, skew-Hermitian matrices, no compsum, no strang_splitting");
+            return QF_ERR_INVALID;
+        }
+        skew = hooks->skewh != 0;
+        forced = hooks->forcing != nullptr || dev_forced;
+        foreign = hooks->hamiltonian != nullptr;
+        time = hooks->time;
+        ctx->w_skew_known = false;
+        ctx->increment_valid = false;
+
+        // states_p: the foreign Hamiltonian returns one stream matrix PER STATE ((k,N,N): np.matmul batches the products)
+        // states_p < 0: the caller does not know yet -- the hook stores 0 or 1 into the field during its FIRST call and the
+        // answer is read back behind that call (no entry probe: the user's function is evaluated as often as the reference
+        // evaluates it); the k stream matrices are reserved up front while that is open
+        per_state = foreign && hooks->states_p > 0 && !magnetic && k > 1;
+        states_p_open = foreign && hooks->states_p < 0 && !magnetic && k > 1;
+        if (per_state && k > 48) return too_many_stream_matrices();
+        return QF_OK;
     }
 
-    auto download_stack = [&](cplx *dst, int which) -> int {     // which: 0 W, 1 Whalf, 2 comm (in PW)
+    // ---- set-up, second half: the buffers, the state on the device, the tolerance
+    int buffers()
+    {
+        QF_TRY(qf_need_matrices(ctx, ctx->multi, per * k + 4 + ((per_state || (states_p_open && k <= 48)) ? (size_t)k : 0)));
+        if (!resident) QF_TRY(qf_need_hook_host(ctx, k));
+        S.resize((size_t)k);
+        for (int j = 0; j < k; ++j) {
+            cplx **b = &ctx->multi[per * j];
+            S[j] = {b[0], {b[1], b[2]}, b[3], b[4], b[5], b[6], 0};
+            if (resident) QF_HIP(hipMemcpyAsync(S[j].W, ctx->W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+            else QF_HIP(hipMemcpyAsync(S[j].W, (const char *)states_host + (size_t)j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));
+            QF_HIP(hipMemsetAsync(S[j].dW[0], 0, mbytes, ctx->stream));                      // dW = zeros_like(W), :430
+            QF_HIP(hipMemcpyAsync(S[j].Whalf, S[j].W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+            if (compsum) QF_HIP(hipMemsetAsync(S[j].kc, 0, mbytes, ctx->stream));             // :457
+        }
+        C3 = ctx->multi[per * k];
+        Bhalf = ctx->multi[per * k + 1], BT = ctx->multi[per * k + 2], BTP = ctx->multi[per * k + 3];
+        hW = ctx->hook_host[0], hP = ctx->hook_host[1], hF = ctx->hook_host[2];
+        slots = (N + TH - 1) / TH;
+        if (!ctx->multi_rowpart) QF_HIP(hipMalloc((void **)&ctx->multi_rowpart, (size_t)2 * slots * N * sizeof(double)));   // (second half: magmp's second state, finite check)
+
+        // tolerance from state 0 (isospectral.py:440-452)
+        if (tol < 0) {
+            double mach_eps = std::numeric_limits<double>::epsilon();
+            if (!compsum) mach_eps = std::sqrt(mach_eps);
+            QF_TRY(auto_tolerance(ctx, S[0].W, mach_eps * dt / qf_hbar(N), &tol));
+        }
+        return QF_OK;
+    }
+
+    int download_stack(cplx *dst, int which)      // which: 0 W, 1 Whalf, 2 comm (in PW)
+    {
         for (int j = 0; j < k; ++j) {
             const cplx *src = which == 0 ? S[j].W : which == 1 ? S[j].Whalf : S[j].PW;
             QF_HIP(hipMemcpyAsync(dst + (size_t)j * NN, src, mbytes, hipMemcpyDeviceToHost, ctx->stream));
         }
         QF_HIP(hipStreamSynchronize(ctx->stream));
         return QF_OK;
-    };
+    }
+
     // half a Strang step on the state (isospectral.py:466-467, 598-599); Whalf = W + dW afterwards
-    auto strang_half = [&]() -> int {
+    int strang_half()
+    {
         if (hooks->strang_table) {
             for (int j = 0; j < k; ++j) {
                 cplx *saveW = ctx->W;
@@ -391,173 +408,138 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
         }
         for (int j = 0; j < k; ++j) QF_TRY(qf_launch_lincomb(ctx, 1.0, S[j].W, 1.0, S[j].dW[S[j].cur], 0.0, S[j].Whalf));
         return QF_OK;
-    };
+    }
 
-    double time = hooks->time;
-    long long total_iterations = 0, number_of_maxit = 0;
-    double resnorm = 0.0;
-    const bool stochastic = dev_forced && ctx->stoch.on;
-    for (int step = 0; step < steps; ++step) {
-        // a stochastic forcing: this step's pattern F0_n, n = the run's counter, drawn into forcing_f0 (three launches,
-        // stochastic.hip); constant over the step's iterations
-        if (stochastic) QF_TRY(qf_launch_stoch_pattern(ctx, ctx->stoch.step + (unsigned long long)step, dt));
-        QF_TRY(strang_half());
-        resnorm = std::numeric_limits<double>::infinity();          // :470
-        // (`reinitialize`: dW was zeroed and Whalf = W set by the previous step's update, or is so at entry)
-        bool broke = false;
-        for (int i = 0; i < maxit; ++i) {
-            total_iterations += 1;                                  // :478
-            bool have_whalf_host = false;
-            // ---- Phalf = vareps * hamiltonian(Whalf)             :488-492
-            if (foreign) {
-                QF_TRY(download_stack(hW, 1));
-                have_whalf_host = true;
-                const int rc = hooks->hamiltonian(hooks->user, hW, hP, hooks->hamiltonian_takes_time ? time + dt / 2 : 0.0);
-                if (rc) return hook_failed("hamiltonian", rc);
-                if (states_p_open) {
-                    states_p_open = false;
-                    per_state = hooks->states_p > 0;
-                    if (per_state && k > 48) {
-                        qf_set_error("qf_isomp_hooked: a Hamiltonian with one stream matrix per state takes at most 48 states (k=%d)", k);
-                        return QF_ERR_UNSUPPORTED;
-                    }
-                }
-                for (size_t e = 0; e < (magnetic ? 2 * NN : per_state ? (size_t)k * NN : NN); ++e) {   // Phalf *= vareps (magmp: Bhalf *= vareps too, mhd.py:375-376)
-                    hP[e].x *= vareps;
-                    hP[e].y *= vareps;
-                }
-                if (per_state) {
-                    for (int j = 0; j < k; ++j) QF_HIP(hipMemcpyAsync(Pj(j), hP + (size_t)j * NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
-                } else {
-                    QF_HIP(hipMemcpyAsync(ctx->Phalf, hP, mbytes, hipMemcpyHostToDevice, ctx->stream));
-                }
-                if (magnetic) QF_HIP(hipMemcpyAsync(Bhalf, hP + NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
+    // ---- Phalf = vareps * hamiltonian(Whalf)             :488-492
+    // *have_whalf_host: the foreign Hamiltonian took Whalf down, the forcing hook need not
+    int stream_matrices(bool *have_whalf_host)
+    {
+        *have_whalf_host = foreign;
+        if (foreign) {
+            QF_TRY(download_stack(hW, 1));
+            const int rc = hooks->hamiltonian(hooks->user, hW, hP, hooks->hamiltonian_takes_time ? time + dt / 2 : 0.0);
+            if (rc) return hook_failed("hamiltonian", rc);
+            if (states_p_open) {
+                states_p_open = false;
+                per_state = hooks->states_p > 0;
+                if (per_state && k > 48) return too_many_stream_matrices();
+            }
+            for (size_t e = 0; e < (magnetic ? 2 * NN : per_state ? (size_t)k * NN : NN); ++e) {   // Phalf *= vareps (magmp: Bhalf *= vareps too, mhd.py:375-376)
+                hP[e].x *= vareps;
+                hP[e].y *= vareps;
+            }
+            if (per_state) {
+                for (int j = 0; j < k; ++j) QF_HIP(hipMemcpyAsync(Pj(j), hP + (size_t)j * NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
             } else {
-                // (the flow's Hamiltonian: an installed one in the skew-Hermitian, non-magnetic mode -- magmp's is solve_mhd)
-                if (hooks->solve_skewh && !magnetic) QF_TRY(qf_launch_hamiltonian(ctx, S[0].Whalf, ctx->Phalf, vareps));
-                else QF_TRY(qf_launch_solve(ctx, ctx->poisson, S[0].Whalf, ctx->Phalf, vareps, hooks->solve_skewh ? 1 : 0));
-                if (magnetic) {      // solve_mhd (mhd.py:10-18): B = laplace(Theta)
-                    QF_TRY(qf_launch_laplace(ctx, S[1].Whalf, Bhalf));
-                    QF_TRY(qf_launch_lincomb(ctx, vareps, Bhalf, 0.0, nullptr, 0.0, Bhalf));
-                }
+                QF_HIP(hipMemcpyAsync(ctx->Phalf, hP, mbytes, hipMemcpyHostToDevice, ctx->stream));
             }
-            // ---- the products                                    :496-505
-            for (int j = 0; j < k; ++j) {
-                QF_TRY(qf_launch_zgemm(ctx, Pj(j), S[j].Whalf, S[j].PW, nullptr));                       // PWcomm = Phalf @ Whalf
-                QF_TRY(qf_launch_zgemm(ctx, S[j].PW, Pj(j), S[j].dW[S[j].cur ^ 1], nullptr));            // dW = PWcomm @ Phalf
-                if (!skew) {                                                                             // PWcomm -= Whalf @ Phalf
-                    QF_TRY(qf_launch_zgemm(ctx, S[j].Whalf, Pj(j), C3, nullptr));
-                    QF_TRY(qf_launch_lincomb(ctx, 1.0, S[j].PW, -1.0, C3, 0.0, S[j].PW));
-                }
+            if (magnetic) QF_HIP(hipMemcpyAsync(Bhalf, hP + NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
+        } else {
+            // (the flow's Hamiltonian: an installed one in the skew-Hermitian, non-magnetic mode -- magmp's is solve_mhd)
+            if (hooks->solve_skewh && !magnetic) QF_TRY(qf_launch_hamiltonian(ctx, S[0].Whalf, ctx->Phalf, vareps));
+            else QF_TRY(qf_launch_solve(ctx, ctx->poisson, S[0].Whalf, ctx->Phalf, vareps, hooks->solve_skewh ? 1 : 0));
+            if (magnetic) {      // solve_mhd (mhd.py:10-18): B = laplace(Theta)
+                QF_TRY(qf_launch_laplace(ctx, S[1].Whalf, Bhalf));
+                QF_TRY(qf_launch_lincomb(ctx, vareps, Bhalf, 0.0, nullptr, 0.0, Bhalf));
             }
-            if (magnetic) {                                         // mhd.py:381,385
-                QF_TRY(qf_launch_zgemm(ctx, Bhalf, S[1].Whalf, BT, nullptr));       // BThetacomm = Bhalf @ Thetahalf
-                QF_TRY(qf_launch_zgemm(ctx, BT, ctx->Phalf, BTP, nullptr));         // BThetaPhalf = BThetacomm @ Phalf
+        }
+        return QF_OK;
+    }
+
+    // ---- the products                                    :496-505
+    int products()
+    {
+        for (int j = 0; j < k; ++j) {
+            QF_TRY(qf_launch_zgemm(ctx, Pj(j), S[j].Whalf, S[j].PW, nullptr));                       // PWcomm = Phalf @ Whalf
+            QF_TRY(qf_launch_zgemm(ctx, S[j].PW, Pj(j), S[j].dW[S[j].cur ^ 1], nullptr));            // dW = PWcomm @ Phalf
+            if (!skew) {                                                                             // PWcomm -= Whalf @ Phalf
+                QF_TRY(qf_launch_zgemm(ctx, S[j].Whalf, Pj(j), C3, nullptr));
+                QF_TRY(qf_launch_lincomb(ctx, 1.0, S[j].PW, -1.0, C3, 0.0, S[j].PW));
             }
-            // ---- forcing(Phalf / vareps, Whalf[, time + dt/2]) * dt/2     :512-520  (before Whalf is rewritten)
-            if (dev_forced) {
-                // the installed forcing, straight into the loop's F: p = Phalf * (1/vareps), F = (dt/2) f -- the roundings of the
-                // host route below
-                QF_TRY(qf_launch_forcing_affine(ctx, ctx->Phalf, S[0].Whalf, S[0].F, 1.0 / vareps, dt / 2));
-            } else if (forced) {
-                if (!foreign) QF_HIP(hipMemcpyAsync(hP, ctx->Phalf, mbytes, hipMemcpyDeviceToHost, ctx->stream));
-                if (!have_whalf_host) QF_TRY(download_stack(hW, 1));
-                else QF_HIP(hipStreamSynchronize(ctx->stream));
-                const double inv = 1.0 / vareps;                    // `Phalf /= vareps`: numpy multiplies by the reciprocal
-                for (size_t e = 0; e < (per_state ? (size_t)k * NN : NN); ++e) {
-                    hP[e].x *= inv;
-                    hP[e].y *= inv;
-                }
-                const int rc = hooks->forcing(hooks->user, hP, hW, hF, hooks->forcing_takes_time ? time + dt / 2 : 0.0);
-                if (rc) return hook_failed("forcing", rc);
-                const double half = dt / 2;
-                for (size_t e = 0; e < (size_t)k * NN; ++e) {       // FW *= dt/2
-                    hF[e].x *= half;
-                    hF[e].y *= half;
-                }
-                for (int j = 0; j < k; ++j)
-                    QF_HIP(hipMemcpyAsync(S[j].F, hF + (size_t)j * NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (magnetic) {                                         // mhd.py:381,385
+            QF_TRY(qf_launch_zgemm(ctx, Bhalf, S[1].Whalf, BT, nullptr));       // BThetacomm = Bhalf @ Thetahalf
+            QF_TRY(qf_launch_zgemm(ctx, BT, ctx->Phalf, BTP, nullptr));         // BThetaPhalf = BThetacomm @ Phalf
+        }
+        return QF_OK;
+    }
+
+    // ---- forcing(Phalf / vareps, Whalf[, time + dt/2]) * dt/2     :512-520  (before Whalf is rewritten)
+    int force_term(bool have_whalf_host)
+    {
+        if (dev_forced) {
+            // the installed forcing, straight into the loop's F: p = Phalf * (1/vareps), F = (dt/2) f -- the roundings of the
+            // host route below
+            QF_TRY(qf_launch_forcing_affine(ctx, ctx->Phalf, S[0].Whalf, S[0].F, 1.0 / vareps, dt / 2));
+        } else if (forced) {
+            if (!foreign) QF_HIP(hipMemcpyAsync(hP, ctx->Phalf, mbytes, hipMemcpyDeviceToHost, ctx->stream));
+            if (!have_whalf_host) QF_TRY(download_stack(hW, 1));
+            else QF_HIP(hipStreamSynchronize(ctx->stream));
+            const double inv = 1.0 / vareps;                    // `Phalf /= vareps`: numpy multiplies by the reciprocal
+            for (size_t e = 0; e < (per_state ? (size_t)k * NN : NN); ++e) {
+                hP[e].x *= inv;
+                hP[e].y *= inv;
             }
-            // ---- comm, dW += comm [+ F], Whalf = W + dW, residual row sums of state 0      :500-534
-            // every state's residual norm is formed: with one stream matrix per state the exit test looks at all of them
-            // (`resnormvec.max()`, :527-532); with a shared one it looks at state 0's, but scipy.linalg.norm checks the WHOLE
-            // stack for infs / NaNs before it reduces (check_finite, :528) -- a NaN in a passively advected state raises
-            // there, so it is an error return here too.  (magmp: state 0's row sums are completed by the magnetic terms
-            // below; the finite check of its second state is the one of qf_isomp_states.)  The result slots scalars[16..63]
-            // take 48 norms; the states beyond them (shared stream matrix only) are wanted for the finite check alone and are
-            // folded on the device into scalars[8] (through scalars[9]).
-            const bool norms_all = per_state || !magnetic;
-            if (norms_all && k > 48 && i + 1 >= minit) QF_HIP(hipMemsetAsync(ctx->scalars + 8, 0, sizeof(double), ctx->stream));
-            for (int j = 0; j < k; ++j) {
-                double *rp = (j == 0 || norms_all) ? ctx->multi_rowpart : (magnetic && j == 1) ? ctx->multi_rowpart + (size_t)slots * N : nullptr;
-                QF_TRY(launch_assemble(ctx, skew, S[j].PW, S[j].dW[S[j].cur ^ 1], (forced && !magnetic) ? S[j].F : nullptr, S[j].W,
-                                       S[j].Whalf, S[j].dW[S[j].cur], rp));
-                if (norms_all && i + 1 >= minit) {
-                    QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + (j < 48 ? 16 + j : 9)));
-                    if (j >= 48) QF_TRY(qf_launch_fold_nonfinite(ctx, ctx->scalars + 9, ctx->scalars + 8));
-                }
-                // magmp: the second state's residual norm, for the finite check alone (its force term has not joined yet: a
-                // non-finite force shows in the next iteration's Whalf)
-                if (magnetic && j == 1 && i + 1 >= minit) QF_TRY(qf_launch_norm_from_rowpart(ctx, rp, slots, ctx->scalars + 17));
+            const int rc = hooks->forcing(hooks->user, hP, hW, hF, hooks->forcing_takes_time ? time + dt / 2 : 0.0);
+            if (rc) return hook_failed("forcing", rc);
+            const double half = dt / 2;
+            for (size_t e = 0; e < (size_t)k * NN; ++e) {       // FW *= dt/2
+                hF[e].x *= half;
+                hF[e].y *= half;
             }
-            if (magnetic) {
-                // the three magnetic updates of dW[0] (mhd.py:389-392), then the force term (:395-402), in that order
-                QF_TRY(qf_launch_magnetic_fix(ctx, BTP, BT, S[0].dW[S[0].cur ^ 1], S[0].dW[S[0].cur], S[0].W, S[0].Whalf,
-                                              ctx->multi_rowpart));
-                if (forced) {
-                    for (int j = 0; j < k; ++j) {
-                        hipLaunchKernelGGL(k_hook_add_forcing, dim3(slots, slots), dim3(256), 0, ctx->stream, N, S[j].F,
-                                           S[j].dW[S[j].cur ^ 1], S[j].dW[S[j].cur], S[j].W, S[j].Whalf,
-                                           j == 0 ? ctx->multi_rowpart : nullptr);
-                        QF_HIP(hipGetLastError());
-                    }
-                }
+            for (int j = 0; j < k; ++j)
+                QF_HIP(hipMemcpyAsync(S[j].F, hF + (size_t)j * NN, mbytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        return QF_OK;
+    }
+
+    // ---- comm, dW += comm [+ F], Whalf = W + dW, residual row sums      :500-534
+    // `norms` (from minit on): every state's residual norm is formed, into the slots of read_stack_resnorm -- with one
+    // stream matrix per state the exit test looks at all of them, with a shared one at state 0's, and the finite check
+    // covers the whole stack either way; the states beyond the 48 slots (shared stream matrix only) are folded on the device
+    // into scalars[8] (through scalars[9]).  magmp: state 0's row sums are completed by the magnetic terms, so its norm is
+    // formed by exit_norm; the second state's is formed here, for the finite check alone (its force term has not joined yet:
+    // a non-finite force shows in the next iteration's Whalf).
+    int assemble_and_norms(bool norms)
+    {
+        if (norms && !magnetic && k > 48) QF_HIP(hipMemsetAsync(ctx->scalars + 8, 0, sizeof(double), ctx->stream));
+        for (int j = 0; j < k; ++j) {
+            double *rp = (j == 0 || !magnetic) ? ctx->multi_rowpart : ctx->multi_rowpart + (size_t)slots * N;
+            QF_TRY(launch_assemble(ctx, skew, S[j].PW, S[j].dW[S[j].cur ^ 1], (forced && !magnetic) ? S[j].F : nullptr, S[j].W,
+                                   S[j].Whalf, S[j].dW[S[j].cur], rp));
+            if (norms && !magnetic) {
+                QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + (j < 48 ? 16 + j : 9)));
+                if (j >= 48) QF_TRY(qf_launch_fold_nonfinite(ctx, ctx->scalars + 9, ctx->scalars + 8));
             }
-            for (int j = 0; j < k; ++j) S[j].cur ^= 1;
-            // ---- exit test on state 0                            :523-536
-            if (i + 1 >= minit) {
-                const double resnorm_old = resnorm;
-                if (norms_all) {
-                    const int kk = k < 48 ? k : 48;
-                    QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 16, (size_t)kk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                    if (k > 48) QF_HIP(hipMemcpyAsync(ctx->host_scalars + 48, ctx->scalars + 8, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                    QF_HIP(hipStreamSynchronize(ctx->stream));
-                    resnorm = ctx->host_scalars[0];
-                    if (k > 48 && !QF_FINITE(ctx->host_scalars[48])) {      // a state beyond the 48 slots: check_finite again
-                        qf_set_error("array must not contain infs or NaNs");
-                        return QF_ERR_NONFINITE;
-                    }
-                    for (int j = 1; j < kk; ++j) {
-                        const double r = ctx->host_scalars[j];
-                        if (per_state) {                 // numpy's max: a NaN wins
-                            if (r != r || resnorm != resnorm) resnorm = std::numeric_limits<double>::quiet_NaN();
-                            else if (r > resnorm) resnorm = r;
-                        } else if (!QF_FINITE(r)) {      // shared stream matrix: state 0's residual decides, check_finite sees every state
-                            qf_set_error("array must not contain infs or NaNs");
-                            return QF_ERR_NONFINITE;
-                        }
-                    }
-                } else {
-                    QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + 1));
-                    QF_TRY(read_scalar(ctx, ctx->scalars + 1, &resnorm));
-                    if (magnetic && k > 1) {
-                        double r1 = 0.0;
-                        QF_TRY(read_scalar(ctx, ctx->scalars + 17, &r1));
-                        if (!QF_FINITE(r1)) resnorm = std::numeric_limits<double>::quiet_NaN();
-                    }
-                }
-                if (!QF_FINITE(resnorm)) {       // scipy.linalg.norm raises here (isospectral.py:534)
-                    qf_set_error("array must not contain infs or NaNs");
-                    return QF_ERR_NONFINITE;
-                }
-                if (resnorm <= tol || resnorm >= resnorm_old) {
-                    broke = true;
-                    break;
+            if (norms && magnetic && j == 1) QF_TRY(qf_launch_norm_from_rowpart(ctx, rp, slots, ctx->scalars + 17));
+        }
+        if (magnetic) {
+            // the three magnetic updates of dW[0] (mhd.py:389-392), then the force term (:395-402), in that order
+            QF_TRY(qf_launch_magnetic_fix(ctx, BTP, BT, S[0].dW[S[0].cur ^ 1], S[0].dW[S[0].cur], S[0].W, S[0].Whalf,
+                                          ctx->multi_rowpart));
+            if (forced) {
+                for (int j = 0; j < k; ++j) {
+                    hipLaunchKernelGGL(k_hook_add_forcing, dim3(slots, slots), dim3(256), 0, ctx->stream, N, S[j].F,
+                                       S[j].dW[S[j].cur ^ 1], S[j].dW[S[j].cur], S[j].W, S[j].Whalf,
+                                       j == 0 ? ctx->multi_rowpart : nullptr);
+                    QF_HIP(hipGetLastError());
                 }
             }
         }
-        if (!broke) number_of_maxit += 1;                           // :538-540
-        // ---- callback(W, 2 comm) before the update               :547-551
+        for (int j = 0; j < k; ++j) S[j].cur ^= 1;
+        return QF_OK;
+    }
+
+    // ---- the exit test's residual norm                   :523-536
+    int exit_norm(double *resnorm)
+    {
+        if (magnetic) QF_TRY(qf_launch_norm_from_rowpart(ctx, ctx->multi_rowpart, slots, ctx->scalars + 16));
+        return read_stack_resnorm(ctx, k, per_state, resnorm);
+    }
+
+    // ---- callback(W, 2 comm) :547-551, then W += 2 comm [+ 2 F];  Whalf = W + dW :553-596, the clock :598-599
+    int step_end()
+    {
         if (hooks->callback) {
             QF_TRY(download_stack(hW, 0));
             QF_TRY(download_stack(hF, 2));
@@ -568,26 +550,62 @@ int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, dou
             const int rc = hooks->callback(hooks->user, hW, hF);
             if (rc) return hook_failed("callback", rc);
         }
-        // ---- W += 2 comm [+ 2 F];  Whalf = W + dW                :553-596
         for (int j = 0; j < k; ++j)
             QF_TRY(launch_update(ctx, S[j].PW, forced ? S[j].F : nullptr, S[j].W, compsum ? S[j].kc : nullptr, S[j].dW[S[j].cur],
                                  reinitialize, S[j].Whalf));
         if (magnetic)                                               // W[0] += 2 BThetacomm (mhd.py:431,438)
             QF_TRY(qf_launch_magnetic_update(ctx, BT, S[0].W, reinitialize ? nullptr : S[0].dW[S[0].cur], S[0].Whalf));
-        if (hooks->has_time) time += dt;                            // :598-599
-        QF_TRY(strang_half());
+        if (hooks->has_time) time += dt;
+        return QF_OK;
+    }
+};
+
+int hooked_body(qf_ctx *ctx, void *states_host, int k, double dt, int steps, double tol, int minit, int maxit,
+                int compsum, int reinitialize, const qf_isomp_hooks *hooks, qf_isomp_stats *stats_out)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(check_iteration_args(minit, maxit));
+    hooked_loop L{ctx, states_host, k, dt, tol, compsum, reinitialize, hooks};
+    QF_TRY(L.setup(steps));
+    QF_TRY(L.buffers());
+    long long total_iterations = 0, number_of_maxit = 0;
+    double resnorm = 0.0;
+    const bool stochastic = L.dev_forced && ctx->stoch.on;
+    for (int step = 0; step < steps; ++step) {
+        // a stochastic forcing: this step's pattern F0_n, n = the run's counter, drawn into forcing_f0 (three launches,
+        // stochastic.hip); constant over the step's iterations
+        if (stochastic) QF_TRY(qf_launch_stoch_pattern(ctx, ctx->stoch.step + (unsigned long long)step, dt));
+        QF_TRY(L.strang_half());
+        resnorm = std::numeric_limits<double>::infinity();          // :470
+        // (`reinitialize`: dW was zeroed and Whalf = W set by the previous step's update, or is so at entry)
+        bool broke = false;
+        for (int i = 0; i < maxit; ++i) {
+            total_iterations += 1;                                  // :478
+            const bool test = i + 1 >= minit;
+            bool have_whalf_host = false;
+            QF_TRY(L.stream_matrices(&have_whalf_host));
+            QF_TRY(L.products());
+            QF_TRY(L.force_term(have_whalf_host));
+            QF_TRY(L.assemble_and_norms(test));
+            if (test) {
+                const double resnorm_old = resnorm;
+                QF_TRY(L.exit_norm(&resnorm));
+                if (resnorm <= L.tol || resnorm >= resnorm_old) {
+                    broke = true;
+                    break;
+                }
+            }
+        }
+        if (!broke) number_of_maxit += 1;                           // :538-540
+        QF_TRY(L.step_end());
+        QF_TRY(L.strang_half());
     }
     if (stochastic) ctx->stoch.step += (unsigned long long)steps;
-    if (resident) QF_HIP(hipMemcpyAsync(ctx->W, S[0].W, mbytes, hipMemcpyDeviceToDevice, ctx->stream));
-    for (int j = 0; j < k && !resident; ++j)
-        QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * mbytes, S[j].W, mbytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (L.resident) QF_HIP(hipMemcpyAsync(ctx->W, L.S[0].W, L.mbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    for (int j = 0; j < k && !L.resident; ++j)
+        QF_HIP(hipMemcpyAsync((char *)states_host + (size_t)j * L.mbytes, L.S[j].W, L.mbytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
-    if (stats_out) {
-        stats_out->total_iterations = total_iterations;
-        stats_out->number_of_maxit = number_of_maxit;
-        stats_out->tol_used = tol;
-        stats_out->last_resnorm = resnorm;
-    }
+    fill_stats(stats_out, total_iterations, number_of_maxit, L.tol, resnorm);
     return QF_OK;
 }
 

@@ -85,6 +85,68 @@ int read_scalar(qf_ctx *ctx, const double *dev, double *out)
     return QF_OK;
 }
 
+// the two iteration arguments of every fixed-point stepper (isospectral.py:400-401; mhd.py: the same assertions)
+int check_iteration_args(int minit, int maxit)
+{
+    if (minit < 1) {
+        qf_set_error("minit must be at least 1.");
+        return QF_ERR_INVALID;
+    }
+    if (maxit < minit) {
+        qf_set_error("maxit must be at minit.");
+        return QF_ERR_INVALID;
+    }
+    return QF_OK;
+}
+
+// what a stepper reports; the caller may not want it
+void fill_stats(qf_isomp_stats *stats_out, long long total_iterations, long long number_of_maxit, double tol, double resnorm)
+{
+    if (!stats_out) return;
+    stats_out->total_iterations = total_iterations;
+    stats_out->number_of_maxit = number_of_maxit;
+    stats_out->tol_used = tol;
+    stats_out->last_resnorm = resnorm;
+}
+
+// The automatic tolerance (isospectral.py:440-452): *tol = prefactor * |X|_inf, the norm through scalars[0] and one read-back.
+// The prefactor is the caller's own expression, so each stepper keeps its rounding.
+int auto_tolerance(qf_ctx *ctx, const cplx *X, double prefactor, double *tol)
+{
+    double nrm = 0.0;
+    QF_TRY(qf_launch_norm_inf(ctx, X, ctx->scalars));
+    QF_TRY(read_scalar(ctx, ctx->scalars, &nrm));
+    *tol = prefactor * nrm;
+    return QF_OK;
+}
+
+// The exit test's read-back for a stack of k states (isospectral.py:523-534).  The loops have put state j's residual norm
+// into scalars[16 + j] for j < 48 and folded the states beyond those 48 slots into scalars[8] (through scalars[9]): one copy
+// of min(k, 48) doubles, the fold flag when k > 48, one synchronisation.  *resnorm is state 0's norm, or with `per_state`
+// (one stream matrix per state) the maximum over the states as numpy forms it (`resnormvec.max()`, :527-532: a NaN wins).
+// scipy.linalg.norm checks the WHOLE stack for infs / NaNs before it reduces (check_finite, :528, :534): a norm that is
+// not finite, of a passively advected state too, is the error it raises.
+int read_stack_resnorm(qf_ctx *ctx, int k, bool per_state, double *resnorm)
+{
+    const int kk = k < 48 ? k : 48;
+    QF_HIP(hipMemcpyAsync(ctx->host_scalars, ctx->scalars + 16, (size_t)kk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (k > 48) QF_HIP(hipMemcpyAsync(ctx->host_scalars + 48, ctx->scalars + 8, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    double r0 = ctx->host_scalars[0];
+    bool finite = QF_FINITE(r0) && (k <= 48 || QF_FINITE(ctx->host_scalars[48]));
+    for (int j = 1; j < kk; ++j) {
+        const double r = ctx->host_scalars[j];
+        finite = finite && QF_FINITE(r);
+        if (per_state && r > r0) r0 = r;
+    }
+    if (!finite) {
+        qf_set_error("array must not contain infs or NaNs");
+        return QF_ERR_NONFINITE;
+    }
+    *resnorm = r0;
+    return QF_OK;
+}
+
 // *out = X is exactly skew-Hermitian (max_ij |X[i,j] + conj(X[j,i])| == 0): what lets a product stand for its mirror image
 int qf_exactly_skew(qf_ctx *ctx, const cplx *X, bool *out)
 {

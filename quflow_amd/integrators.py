@@ -159,6 +159,61 @@ def _forcing_on(ctx, aff):
             aff.uninstall(ctx)
 
 
+def _check_iterations(minit, maxit):
+    """AssertionError like isospectral.py:400-401 (and mhd.py), for every fixed-point stepper and resident `advance`."""
+    assert minit >= 1, "minit must be at least 1."
+    assert maxit >= minit, "maxit must be at minit."
+
+
+def _tol_arg(tol):
+    """The `tol` argument as the float of the C entries: 'auto' and negative values mean the automatic tolerance (a negative
+    float goes through as it is, isospectral.py:440); any other string is the reference's TypeError."""
+    if isinstance(tol, str):
+        if tol != 'auto':
+            raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
+        return -1.0
+    return float(tol)
+
+
+def _report_iterations(stats, verbatim, st, steps, maxit_key='number_of_maxit'):
+    """The per-step averages of a call (isospectral.py:609-611, mhd.py:451-453): printed with `verbatim`, written into `stats`
+    unless it is None; nothing for an empty call."""
+    if steps <= 0:
+        return
+    if verbatim:
+        print("Average number of iterations per step: {:.2f}".format(st.total_iterations / steps))
+    if stats is not None:
+        stats["iterations"] = st.total_iterations / steps
+        stats[maxit_key] = st.number_of_maxit / steps
+
+
+def _report(stats, verbatim, st, steps, auto, tol_report, tol_key='tol_auto', maxit_key='number_of_maxit'):
+    """What a fixed-point stepper says after its C call: with an automatic tolerance "Tolerance set to" and stats[tol_key]
+    (isospectral.py:451-452; `tol_report` where the host computed it, else what the device used), then the averages.  `stats`
+    is written only if truthy, as the reference tests it.  The differences between the steppers are kept as they were:
+      * _isomp_stepwise_on reports the tolerance before its loop, from the host formula (_report_tolerance), and the averages
+        of its own sums after it;
+      * magmp's keys are 'tol' and 'maxit' (mhd.py:341,452-454);
+      * isomp_quasinewton writes stats['tol'] always and tests `stats is not None`: it uses _report_iterations alone."""
+    if auto:
+        _report_tolerance(stats, verbatim, st.tol_used if tol_report is None else tol_report, tol_key)
+    _report_iterations(stats if stats else None, verbatim, st, steps, maxit_key)
+
+
+def _report_tolerance(stats, verbatim, tol_used, tol_key='tol_auto'):
+    """The automatic tolerance of a call (isospectral.py:451-452): printed with `verbatim`, written into a truthy `stats`."""
+    if verbatim:
+        print("Tolerance set to {}.".format(tol_used))
+    if stats:
+        stats[tol_key] = tol_used
+
+
+def _stats_dict(st, steps):
+    """The statistics a resident `advance` returns (bench.py and the tools read these keys)."""
+    return {"iterations": st.total_iterations / max(steps, 1), "number_of_maxit": st.number_of_maxit / max(steps, 1),
+            "total_iterations": st.total_iterations, "tol": st.tol_used, "last_resnorm": st.last_resnorm}
+
+
 def isomp_fixedpoint(W,
                      dt,
                      steps=100,
@@ -197,9 +252,7 @@ def isomp_fixedpoint(W,
         on the device context for the call and one kernel forms the force term inside that loop (nothing crosses PCIe
         for it); a TridiagonalHamiltonian and a ViscDampStep are followed on the device next to it.
     """
-    # Check input (AssertionError like isospectral.py:400-401)
-    assert minit >= 1, "minit must be at least 1."
-    assert maxit >= minit, "maxit must be at minit."
+    _check_iterations(minit, maxit)
 
     # a TridiagonalHamiltonian is followed on the device (installed for this call): native in every route below
     ham = _installable(hamiltonian, W)
@@ -254,17 +307,7 @@ def isomp_fixedpoint(W,
     if Wc is not W:
         W[...] = Wc                  # in-place contract
 
-    if auto:
-        tol_used = st.tol_used if tol_report is None else tol_report
-        if verbatim:
-            print("Tolerance set to {}.".format(tol_used))
-        if stats:
-            stats['tol_auto'] = tol_used                  # isospectral.py:451-452
-    if verbatim and steps > 0:
-        print("Average number of iterations per step: {:.2f}".format(st.total_iterations / steps))
-    if stats and steps > 0:                               # isospectral.py:609-611
-        stats["iterations"] = st.total_iterations / steps
-        stats["number_of_maxit"] = st.number_of_maxit / steps
+    _report(stats, verbatim, st, steps, auto, tol_report)
     return W
 
 
@@ -283,11 +326,7 @@ def _device_tol(W, dt, tol, compsum):
     automatic double-precision tolerance (read back as stats.tol_used); complex64 input gets the
     reference's single-precision tolerance, evaluated here from the input, so that a complex64 run stops
     where the reference's does although the arithmetic on the device is double precision."""
-    if isinstance(tol, str):
-        if tol != 'auto':
-            raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
-        tol = -1.0
-    tol = float(tol)
+    tol = _tol_arg(tol)
     if tol < 0 and W.dtype == np.complex64:
         t = float(_auto_tol(W, dt, compsum))
         return t, t
@@ -301,8 +340,7 @@ def _isomp_stepwise(W, dt, steps, strang_splitting, stats, callback, tol, maxit,
                                   reinitialize, device)
     if not isinstance(W, np.ndarray) or W.ndim != 2 or W.shape[0] != W.shape[1]:
         raise ValueError("W must be a square matrix")
-    if isinstance(tol, str) and tol != 'auto':
-        raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
+    _tol_arg(tol)
     # (an installed TridiagonalHamiltonian: the same loop, on the same stepper context, with it in force)
     with _hamiltonian_on(get_stepper_context(W.shape[-1], device), ham):
         return _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
@@ -317,20 +355,13 @@ def _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, max
     if not isinstance(W, np.ndarray) or W.ndim != 2 or W.shape[0] != W.shape[1]:
         raise ValueError("W must be a square matrix")
     N = W.shape[-1]
-    if isinstance(tol, str) and tol != 'auto':
-        raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
+    tol_c = _tol_arg(tol)
     ctx = get_stepper_context(N, device)      # the hooks may use the shared context (solve_viscdamp, energy_euler, ...)
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
-    auto = isinstance(tol, str) or tol < 0
-    tol_c = float(_auto_tol(W, dt, compsum)) if auto else float(tol)
-    if auto:
-        if verbatim:
-            print("Tolerance set to {}.".format(tol_c))
-        if stats:
-            stats['tol_auto'] = tol_c
-    total_iterations = 0.0
-    number_of_maxit = 0.0
-    st = _lib.IsompStats()
+    if tol_c < 0:
+        tol_c = float(_auto_tol(W, dt, compsum))
+        _report_tolerance(stats, verbatim, tol_c)         # (known before the loop)
+    st, total = _lib.IsompStats(), _lib.IsompStats()      # (one step's record; the call's sums, for the report)
     PW = np.zeros((N, N), dtype=np.complex128) if callback is not None else None
     on_device = False
     resident_strang = isinstance(strang_splitting, _laplacian.ViscDampStep)
@@ -355,8 +386,8 @@ def _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, max
         step = ctx._lib.qf_isomp if k == 0 else ctx._lib.qf_isomp_continue
         _lib.check(step(ctx.handle, float(dt), 1, float(tol_c), int(minit), int(maxit), int(bool(compsum)),
                         int(bool(reinitialize)), ctypes.byref(st)))
-        total_iterations += st.total_iterations
-        number_of_maxit += st.number_of_maxit
+        total.total_iterations += st.total_iterations
+        total.number_of_maxit += st.number_of_maxit
         if callback is not None:
             # PWcomm of the last iteration, doubled (isospectral.py:547-550), from the device's PW
             _lib.check(ctx._lib.qf_download_buffer(ctx.handle, _lib.BUFFER_IDS["PW"], ptr(PW)))
@@ -370,11 +401,7 @@ def _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, max
     if on_device:
         _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     W[...] = Wc
-    if verbatim and steps > 0:
-        print("Average number of iterations per step: {:.2f}".format(total_iterations / steps))
-    if stats and steps > 0:
-        stats["iterations"] = total_iterations / steps
-        stats["number_of_maxit"] = number_of_maxit / steps
+    _report(stats, verbatim, total, steps, False, None)
     return W
 
 
@@ -521,8 +548,7 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
     device and calls back for what only Python can compute."""
     if W.ndim not in (2, 3) or W.shape[-1] != W.shape[-2]:
         raise ValueError("W must be a square matrix or a (k,N,N) stack")
-    if isinstance(tol, str) and tol != 'auto':
-        raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
+    _tol_arg(tol)
     N = W.shape[-1]
     squeeze = W.ndim == 2
     k = 1 if squeeze else W.shape[0]
@@ -545,12 +571,21 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
         table.set_strang(strang_splitting)
     if callback is not None:
         table.set_callback(callback)
+    tol_c, tol_report = _device_tol(W, dt, tol, compsum)
+    return _hooked_call(table, W, Wc, k, dt, steps, time, tol, tol_c, tol_report, minit, maxit, compsum, reinitialize, stats,
+                        verbatim, device, 'tol_auto', 'number_of_maxit', ham=ham, aff=aff)
+
+
+def _hooked_call(table, W, Wc, k, dt, steps, time, tol, tol_c, tol_report, minit, maxit, compsum, reinitialize, stats, verbatim,
+                 device, tol_key, maxit_key, ham=None, aff=None):
+    """What _isomp_hooked and _magmp_hooked share once their table is set up: the table's time fields, the stepper context,
+    qf_isomp_hooked with the call's Hamiltonian / forcing installed, the hooks' exception or the library's error, the copy
+    back into the caller's array and the report."""
     table.c.has_time = int(time is not None)
     table.c.time = float(time) if time is not None else 0.0
     auto = isinstance(tol, str) or tol < 0
-    ctx = get_stepper_context(N, device)
+    ctx = get_stepper_context(W.shape[-1], device)
     st = _lib.IsompStats()
-    tol_c, tol_report = _device_tol(W, dt, tol, compsum)
     with _hamiltonian_on(ctx, ham), _forcing_on(ctx, aff):       # (`native`: the device's own solve, of what is installed)
         rc = ctx._lib.qf_isomp_hooked(ctx.handle, ptr(Wc), k, float(dt), int(steps), tol_c, int(minit),
                                       int(maxit), int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(table.c),
@@ -558,17 +593,7 @@ def _isomp_hooked(W, dt, steps, hamiltonian, native, time, forcing, strang_split
     table.check(rc)
     if Wc is not W:
         W[...] = Wc
-    if auto:
-        tol_used = st.tol_used if tol_report is None else tol_report
-        if verbatim:
-            print("Tolerance set to {}.".format(tol_used))
-        if stats:
-            stats['tol_auto'] = tol_used
-    if verbatim and steps > 0:
-        print("Average number of iterations per step: {:.2f}".format(st.total_iterations / steps))
-    if stats and steps > 0:
-        stats["iterations"] = st.total_iterations / steps
-        stats["number_of_maxit"] = st.number_of_maxit / steps
+    _report(stats, verbatim, st, steps, auto, tol_report, tol_key, maxit_key)
     return W
 
 
@@ -577,8 +602,7 @@ def _magmp_hooked(W, dt, steps, hamiltonian, native_mhd, time, forcing, stats, c
     """magmp_fixedpoint with host hooks (quflow/integrators/mhd.py:235-456): qf_isomp_hooked in its magnetic mode --
     the (2,N,N) state, dW, the products and the magnetic terms stay on the device; a foreign Hamiltonian returns the
     pair (P, B), `forcing(P, state)` a (2,N,N) force, `callback(state, 2 PWcomm)` host copies."""
-    if isinstance(tol, str) and tol != 'auto':
-        raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
+    tol_c = _tol_arg(tol)
     if not (_SKEW_HERM_ and _laplacian._SKEW_HERM_):
         raise NotImplementedError("magmp on the HIP path is for skew-Hermitian matrices (select_skewherm(True)).")
     N = W.shape[-1]
@@ -591,28 +615,9 @@ def _magmp_hooked(W, dt, steps, hamiltonian, native_mhd, time, forcing, stats, c
         table.set_hamiltonian_pair(hamiltonian, _takes_time(hamiltonian, (Wc,), time))
     if callback is not None:
         table.set_callback(callback)
-    table.c.has_time = int(time is not None)
-    table.c.time = float(time) if time is not None else 0.0
-    auto = isinstance(tol, str) or tol < 0
-    tol_c = -1.0 if auto else float(tol)
-    ctx = get_stepper_context(N, device)
-    st = _lib.IsompStats()
-    rc = ctx._lib.qf_isomp_hooked(ctx.handle, ptr(Wc), 2, float(dt), int(steps), tol_c, int(minit), int(maxit), 0,
-                                  int(bool(reinitialize)), ctypes.byref(table.c), ctypes.byref(st))
-    table.check(rc)
-    if Wc is not W:
-        W[...] = Wc
-    if auto:
-        if verbatim:
-            print("Tolerance set to {}.".format(st.tol_used))
-        if stats:
-            stats['tol'] = st.tol_used                     # mhd.py:344-345
-    if verbatim and steps > 0:
-        print("Average number of iterations per step: {:.2f}".format(st.total_iterations / steps))
-    if stats and steps > 0:                                # mhd.py:451-453
-        stats["iterations"] = st.total_iterations / steps
-        stats["maxit"] = st.number_of_maxit / steps
-    return W
+    # (the device's tolerance whatever the dtype; the keys of mhd.py:344-345, 451-453)
+    return _hooked_call(table, W, Wc, 2, dt, steps, time, tol, -1.0 if tol_c < 0 else tol_c, None, minit, maxit, False,
+                        reinitialize, stats, verbatim, device, 'tol', 'maxit')
 
 
 def _isomp_states(W, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats, verbatim, device,
@@ -629,17 +634,7 @@ def _isomp_states(W, dt, steps, tol, minit, maxit, reinitialize, magnetic, stats
                                             int(maxit), int(bool(reinitialize)), int(bool(magnetic)), ctypes.byref(st)))
     if Wc is not W:
         W[...] = Wc
-    if auto:
-        tol_used = st.tol_used if tol_report is None else tol_report
-        if verbatim:
-            print("Tolerance set to {}.".format(tol_used))
-        if stats:
-            stats[tol_key] = tol_used
-    if verbatim and steps > 0:
-        print("Average number of iterations per step: {:.2f}".format(st.total_iterations / steps))
-    if stats and steps > 0:
-        stats["iterations"] = st.total_iterations / steps
-        stats[maxit_key] = st.number_of_maxit / steps
+    _report(stats, verbatim, st, steps, auto, tol_report, tol_key, maxit_key)
     return W
 
 
@@ -670,8 +665,7 @@ def magmp_fixedpoint(W, dt, steps=100, hamiltonian=solve_mhd, time=None, forcing
     iteration, the Poisson solve, the Laplacian and the updates run on the device (qf_isomp_states
     with magnetic=1).  stats receives 'tol', 'iterations', 'maxit' like the reference (:341,452-454).
     """
-    assert minit >= 1, "minit must be at least 1."
-    assert maxit >= minit, "maxit must be at minit."
+    _check_iterations(minit, maxit)
     _refuse_stochastic(forcing, "magmp")
     if not isinstance(W, np.ndarray) or W.ndim != 3 or W.shape[0] != 2 or W.shape[1] != W.shape[2]:
         raise ValueError("the MHD state must be a (2,N,N) ndarray (W, Theta)")
@@ -750,12 +744,7 @@ def isomp_quasinewton(W, dt, steps=100, hamiltonian=_laplacian.solve_poisson, fo
     steps = _reference_args(W, steps)
     if steps == 0 and not np.issubdtype(W.dtype, np.complexfloating):
         return W                 # the reference's empty loop never touches a real / integer W
-    if isinstance(tol, str):
-        if tol != "auto":
-            raise TypeError("tol must be a float or 'auto' (the reference compares it with a number: '<' not supported between instances of 'str' and 'int')")
-        tol_c = -1.0
-    else:
-        tol_c = float(tol)
+    tol_c = _tol_arg(tol)
     if tol_c < 0 and W.dtype == np.complex64:
         # isospectral.py:194-195 with the machine epsilon of the input's precision
         tol_c = float(np.finfo(np.float32).eps * (dt / hbar(W.shape[-1])) * np.linalg.norm(W, np.inf))
@@ -780,12 +769,9 @@ def isomp_quasinewton(W, dt, steps=100, hamiltonian=_laplacian.solve_poisson, fo
     _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     if Wc is not W:
         W[...] = Wc
-    if verbatim and steps > 0:
-        print("Average number of iterations per step: {:.2f}".format(st.total_iterations / steps))
     stats = kwargs.get("stats")
+    _report_iterations(stats, verbatim, st, steps)
     if stats is not None and steps > 0:
-        stats["iterations"] = st.total_iterations / steps
-        stats["number_of_maxit"] = st.number_of_maxit / steps
         stats["tol"] = st.tol_used
     return W
 
@@ -927,9 +913,20 @@ class DeviceTrajectory:
     semantics of one `integrator(W, dt, steps=...)` call of simulation.solve
     (quflow/simulation.py:782-798): dW restarts from zero (isospectral.py:430)."""
 
-    forcing = None              # (class defaults: from_shr / from_fun build instances without __init__)
+    forcing = None              # (class defaults: _bare builds instances without __init__)
     strang_splitting = None
     hamiltonian = None
+
+    @classmethod
+    def _bare(cls, N, device=None, ctx=None):
+        """A complex128 trajectory without a state of its own yet, on `ctx` or on a new private context: what from_shr / from_fun
+        fill and what a DeviceStackTrajectory reaches its members through."""
+        self = cls.__new__(cls)
+        self.N, self.c64, self.dtype = int(N), False, np.complex128
+        self.ctx = Context(self.N, default_device() if device is None else device) if ctx is None else ctx
+        self._lib = self.ctx._lib
+        self.hamiltonian = None
+        return self
 
     def __init__(self, W0, device=None, hamiltonian=None, forcing=None, strang_splitting=None):
         """`hamiltonian`: None / solve_poisson for the built-in one, or a TridiagonalHamiltonian, which is installed on the
@@ -1033,8 +1030,7 @@ class DeviceTrajectory:
         """`diagnostics=True`: energy_euler and enstrophy of the new state come back with the statistics
         (keys "energy", "enstrophy"), computed behind the last step under the call's one synchronisation
         (qf_isomp_diag) -- what an output chunk of simulation.solve logs (quflow/simulation.py:788-803)."""
-        assert minit >= 1, "minit must be at least 1."
-        assert maxit >= minit, "maxit must be at minit."
+        _check_iterations(minit, maxit)
         tol_c = -1.0 if isinstance(tol, str) else float(tol)
         st = _lib.IsompStats()
         args = (self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit), int(bool(compsum)),
@@ -1073,10 +1069,7 @@ class DeviceTrajectory:
             out = {"energy": e.value, "enstrophy": s.value}
         else:
             _lib.check(self._lib.qf_isomp(*args))
-        out.update({"iterations": st.total_iterations / max(steps, 1),
-                    "number_of_maxit": st.number_of_maxit / max(steps, 1),
-                    "total_iterations": st.total_iterations, "tol": st.tol_used,
-                    "last_resnorm": st.last_resnorm})
+        out.update(_stats_dict(st, steps))
         return out
 
     def advance_erk(self, method, dt, steps):
@@ -1100,8 +1093,7 @@ class DeviceTrajectory:
         else:
             _lib.check(self._lib.qf_isomp_quasinewton(self.ctx.handle, float(dt), int(steps), float(tol), int(maxit),
                                                       ctypes.byref(st)))
-        return {"iterations": st.total_iterations / max(steps, 1), "number_of_maxit": st.number_of_maxit / max(steps, 1),
-                "total_iterations": st.total_iterations, "tol": st.tol_used, "last_resnorm": st.last_resnorm}
+        return _stats_dict(st, steps)
 
     def _double_only(self, what):
         if self.c64:
@@ -1141,12 +1133,7 @@ class DeviceTrajectory:
         omega = np.ascontiguousarray(omega, dtype=np.float64)
         if N == -1:
             N = round(np.sqrt(omega.shape[0]))
-        self = cls.__new__(cls)
-        self.N = int(N)
-        self.c64 = False
-        self.dtype = np.complex128
-        self.ctx = Context(self.N, default_device() if device is None else device)
-        self._lib = self.ctx._lib
+        self = cls._bare(N, device)
         self._need_basis()
         _lib.check(self._lib.qf_shr2mat(self.ctx.handle, ptr(omega), ctypes.c_longlong(omega.shape[0]), None))
         return self
@@ -1165,12 +1152,7 @@ class DeviceTrajectory:
         N = int(N)
         if L > N:
             raise ValueError("from_fun: the grid's bandwidth L=%d exceeds the matrix size N=%d" % (L, N))
-        self = cls.__new__(cls)
-        self.N = N
-        self.c64 = False
-        self.dtype = np.complex128
-        self.ctx = Context(self.N, default_device() if device is None else device)
-        self._lib = self.ctx._lib
+        self = cls._bare(N, device)
         self._need_basis()
         _lib.check(self._lib.qf_fun2shr(self.ctx.handle, ptr(f), L, 1, None))
         _lib.check(self._lib.qf_shr2mat(self.ctx.handle, None, ctypes.c_longlong(L * L), None))
@@ -1294,9 +1276,7 @@ class DeviceStackTrajectory:
         self.ctx = Context(self.N, default_device() if device is None else device)
         self._lib = self.ctx._lib
         # member access: a DeviceTrajectory's resident helpers on this context's state W, where qf_states_select puts member j
-        self._member = DeviceTrajectory.__new__(DeviceTrajectory)
-        self._member.N, self._member.c64, self._member.dtype = self.N, False, np.complex128
-        self._member.ctx, self._member._lib, self._member.hamiltonian = self.ctx, self._lib, None
+        self._member = DeviceTrajectory._bare(self.N, ctx=self.ctx)
         try:
             _lib.check(self._lib.qf_states_upload(self.ctx.handle, ptr(states0), self.k))
         except Exception:
@@ -1306,8 +1286,7 @@ class DeviceStackTrajectory:
     def advance(self, dt, steps, tol='auto', maxit=10, minit=1, reinitialize=False, diagnostics=False):
         """The keys of DeviceTrajectory.advance; `diagnostics=True` adds `diagnostics()` of the new state -- for MHD queued
         behind the last step under the call's closing synchronisation (qf_states_advance_diag)."""
-        assert minit >= 1, "minit must be at least 1."
-        assert maxit >= minit, "maxit must be at minit."
+        _check_iterations(minit, maxit)
         tol_c = -1.0 if isinstance(tol, str) else float(tol)
         st = _lib.IsompStats()
         args = (self.ctx.handle, float(dt), int(steps), tol_c, int(minit), int(maxit), int(bool(reinitialize)),
@@ -1321,10 +1300,7 @@ class DeviceStackTrajectory:
             _lib.check(self._lib.qf_states_advance(*args))
             if diagnostics:
                 out = self.diagnostics()
-        out.update({"iterations": st.total_iterations / max(steps, 1),
-                    "number_of_maxit": st.number_of_maxit / max(steps, 1),
-                    "total_iterations": st.total_iterations, "tol": st.tol_used,
-                    "last_resnorm": st.last_resnorm})
+        out.update(_stats_dict(st, steps))
         return out
 
     def diagnostics(self):
@@ -1425,8 +1401,7 @@ class DeviceEnsemble:
         member's is {"failed": True, "tol": ...}).  A failed member holds the state its own DeviceTrajectory.advance would
         leave on that failure (after its last completed step); every other member has advanced all `steps` steps, exactly
         as alone.  Any other error raises at once."""
-        assert minit >= 1, "minit must be at least 1."
-        assert maxit >= minit, "maxit must be at minit."
+        _check_iterations(minit, maxit)
         tol_c = -1.0 if isinstance(tol, str) else float(tol)
         for m in self.members:
             _refuse_stochastic(m.forcing, "DeviceEnsemble.advance")
@@ -1447,8 +1422,7 @@ class DeviceEnsemble:
                     failed.append(g0 + r)
                     out.append({"failed": True, "tol": s.tol_used})
                     continue
-                out.append({"iterations": s.total_iterations / max(steps, 1), "number_of_maxit": s.number_of_maxit / max(steps, 1),
-                            "total_iterations": s.total_iterations, "tol": s.tol_used, "last_resnorm": s.last_resnorm})
+                out.append(_stats_dict(s, steps))
         if failed:
             err = ValueError("array must not contain infs or NaNs (DeviceEnsemble members %s)" % ", ".join(map(str, failed)))
             err.failed = failed

@@ -516,11 +516,23 @@ def create_runfile(sim, runfilename=None):
     return runfilename
 
 
+# the keyword arguments a resident trajectory can carry, once per stepper family: any other key keeps a run on the host path
+_ISOMP_RESIDENT_KEYS = frozenset(("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim",
+                                  "forcing", "strang_splitting", "callback"))
+_MAGMP_RESIDENT_KEYS = frozenset(("time", "hamiltonian", "stats", "tol", "maxit", "minit", "reinitialize", "verbatim", "forcing",
+                                  "callback"))
+
+
+def _is_isomp(integrator):
+    from . import integrators as _int
+    return integrator in (_int.isomp, _int.isomp_fixedpoint) or isinstance(integrator, _int.IsompHIP)
+
+
 def _device_resident_ok(integrator, kwargs):
     """The default stepper without host hooks: the trajectory may stay on the device between chunks."""
     from . import integrators as _int
     from . import laplacian as _lap
-    if integrator not in (_int.isomp, _int.isomp_fixedpoint) and not isinstance(integrator, _int.IsompHIP):
+    if not _is_isomp(integrator):
         return False
     if kwargs.get("callback") is not None:
         return False
@@ -532,8 +544,7 @@ def _device_resident_ok(integrator, kwargs):
         return False
     if (forcing is not None or strang is not None) and kwargs.get("compsum"):
         return False
-    if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim", "forcing",
-                     "strang_splitting", "callback") for k in kwargs):
+    if any(k not in _ISOMP_RESIDENT_KEYS for k in kwargs):
         return False
     h = kwargs.get("hamiltonian")
     # (a TridiagonalHamiltonian is installed on the resident trajectory's context: as native as the built-in one)
@@ -546,8 +557,8 @@ def _resident_kind(integrator, ikw, W):
     AffineForcing / StochasticForcing, no Strang step or a ViscDampStep, no callback, no compsum next to a forcing or a Strang step -- on an (N,N)
     complex128 state, or complex64 without those device objects), 'stack'
     (DeviceStackTrajectory: isomp on a (k,N,N) complex128 stack, built-in Hamiltonian, no compsum), 'mhd'
-    (DeviceMHDTrajectory: magmp with hamiltonian = solve_mhd on a (2,N,N) complex128 state) or None.  Pure: nothing is
-    created or touched."""
+    (DeviceMHDTrajectory: magmp with hamiltonian = solve_mhd on a (2,N,N) complex128 state) or None.  The only place that
+    decides: `solve` builds its trajectory from this value and nothing else.  Pure: nothing is created or touched."""
     from . import integrators as _int
     from . import laplacian as _lap
     W = np.asarray(W)
@@ -564,15 +575,13 @@ def _resident_kind(integrator, ikw, W):
     if ikw.get("forcing") is not None or ikw.get("callback") is not None:
         return None
     if integrator in (_int.magmp, _int.magmp_fixedpoint):
-        if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "reinitialize", "verbatim", "forcing", "callback")
-               for k in ikw):
+        if any(k not in _MAGMP_RESIDENT_KEYS for k in ikw):
             return None
         return 'mhd' if ikw.get("hamiltonian") is _int.solve_mhd and W.shape[0] == 2 else None
-    if integrator in (_int.isomp, _int.isomp_fixedpoint) or isinstance(integrator, _int.IsompHIP):
+    if _is_isomp(integrator):
         if ikw.get("strang_splitting") is not None or ikw.get("compsum"):
             return None
-        if any(k not in ("time", "hamiltonian", "stats", "tol", "maxit", "minit", "compsum", "reinitialize", "verbatim", "forcing",
-                         "callback", "strang_splitting") for k in ikw):
+        if any(k not in _ISOMP_RESIDENT_KEYS for k in ikw):
             return None
         return 'stack' if _int._is_native_hamiltonian(ikw.get("hamiltonian")) else None
     return None
@@ -597,7 +606,8 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
     resident: keep the trajectory on the device between the chunks (default: whenever the stepper is
     quflow_amd.isomp with its built-in or a tridiagonal Hamiltonian and no host hooks -- an AffineForcing, a StochasticForcing
     and a ViscDampStep are device objects, not hooks --, on a complex128 (N,N) state or a
-    (k,N,N) stack, or quflow_amd.magmp with hamiltonian=solve_mhd on the (2,N,N) MHD state: _resident_kind).
+    (k,N,N) stack, or quflow_amd.magmp with hamiltonian=solve_mhd on the (2,N,N) MHD state: _resident_kind).  True means
+    what the default means -- a run the trajectory cannot carry takes the host path --; False always takes the host path.
     As in the reference the caller's array is advanced in place (isomp overwrites W) and the final
     state is returned."""
     from . import integrators as _int
@@ -680,26 +690,23 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
             pbar = None
 
     W_caller = W
-    use_device = _device_resident_ok(integrator, ikw) if resident is None else bool(resident)
+    # _resident_kind decides, once: `resident=True` means what the default means, and a run the trajectory cannot carry (a host
+    # forcing / Strang callable, a callback, a foreign Hamiltonian, another stepper) takes the host path whatever `resident` says
+    kind = None if resident is False else _resident_kind(integrator, ikw, W)
     tr = None
-    # (a complex64 state makes a single-precision resident trajectory: float32 solve, complex64 products and the
-    # float32 tolerance rule, exactly what isomp does with a complex64 host array)
-    ham = ikw.get('hamiltonian') if isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian) else None
-    # an AffineForcing and a ViscDampStep travel with the resident trajectory; a run with any other forcing / Strang callable
-    # (or with compsum next to them) is not resident, whatever `resident` says: the trajectory could not apply them
-    forcing, strang = ikw.get('forcing'), ikw.get('strang_splitting')
-    if (forcing is not None or strang is not None) and _resident_kind(integrator, ikw, W) != 'single':
-        use_device = False
-    if use_device and W.ndim == 2 and W.dtype in (np.complex128, np.complex64) and (ham is None or W.dtype == np.complex128):
-        tr = _int.DeviceTrajectory(W, hamiltonian=ham, forcing=forcing, strang_splitting=strang)
+    forcing = ikw.get('forcing')
+    if kind == 'single':
+        # (a complex64 state makes a single-precision resident trajectory: float32 solve, complex64 products and the
+        # float32 tolerance rule, exactly what isomp does with a complex64 host array; an AffineForcing, a StochasticForcing,
+        # a ViscDampStep and a TridiagonalHamiltonian travel with the trajectory)
+        ham = ikw.get('hamiltonian') if isinstance(ikw.get('hamiltonian'), _lap.TridiagonalHamiltonian) else None
+        tr = _int.DeviceTrajectory(W, hamiltonian=ham, forcing=forcing, strang_splitting=ikw.get('strang_splitting'))
         adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "compsum", "reinitialize") if k in ikw}
-    # a (k,N,N) stack under isomp, the MHD pair under magmp: resident too unless resident=False
-    stack_kind = _resident_kind(integrator, ikw, W) if (resident is None or resident) and W.ndim == 3 else None
-    if stack_kind in ('stack', 'mhd'):
-        tr = _int.DeviceStackTrajectory(W, magnetic=(stack_kind == 'mhd'))
+    elif kind is not None:
+        # a (k,N,N) stack under isomp, the MHD pair under magmp
+        tr = _int.DeviceStackTrajectory(W, magnetic=(kind == 'mhd'))
         adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "reinitialize") if k in ikw}
-    else:
-        stack_kind = None
+    stack_kind = kind if kind in ('stack', 'mhd') else None
     want_shr = any(isinstance(c, Simulation) and 'shr' in c.qutypes for c in (callback or ()))
     try:
         for k0 in range(0, steps, max(steps_out, 1)):

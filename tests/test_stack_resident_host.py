@@ -109,3 +109,57 @@ def test_resident_kind():
     # _device_resident_ok keeps its meaning
     assert simulation._device_resident_ok(qfa.isomp, poisson) is True
     assert simulation._device_resident_ok(qfa.magmp, mhd) is False
+
+
+class _Resident(Exception):
+    """solve built a resident trajectory."""
+
+
+class _HostPath(Exception):
+    """solve called the integrator, which asked for its device context."""
+
+
+def test_solve_resident_is_one_decision(monkeypatch):
+    """`resident=True` means what the default means: a run the trajectory cannot carry takes the host path with the stepper,
+    the Hamiltonian and the hooks the caller named; `resident=False` always does.  Only the decision is under test: the
+    trajectories and the integrators' contexts are stubs that say which way `solve` went."""
+    def resident(*a, **k):
+        raise _Resident()
+
+    def host(*a, **k):
+        raise _HostPath()
+
+    monkeypatch.setattr(integrators, "DeviceTrajectory", resident)
+    monkeypatch.setattr(integrators, "DeviceStackTrajectory", resident)
+    monkeypatch.setattr(integrators, "get_context", host)
+    monkeypatch.setattr(integrators, "get_stepper_context", host)
+    N = 8
+    W2, W3, M = skew(N, 1)[0], skew(N, 3), skew(N, 2)
+
+    def rk4_stub(W, dt, steps=100, **kw):      # (rk4 takes no `time`, which solve passes to every stepper: stubbed, as the
+        raise _HostPath()                      # test is about the decision and not about that signature)
+
+    monkeypatch.setattr(integrators, "rk4", rk4_stub)
+    monkeypatch.setattr(qfa, "rk4", rk4_stub)
+
+    def went(W, **kw):
+        with pytest.raises((_Resident, _HostPath)) as info:
+            qfa.solve(W.copy(), dt=1e-3, steps=1, progress_bar=False, **kw)
+        return info.type
+
+    not_carried = (dict(integrator=qfa.rk4),
+                   dict(integrator=qfa.isomp_quasinewton),
+                   dict(hamiltonian=lambda W: W),
+                   dict(integrator_callback=lambda W, dW: None),
+                   dict(forcing=lambda P, W: 0.0 * W))
+    for kw in not_carried:
+        assert went(W2, resident=True, **kw) is _HostPath, kw
+        assert went(W2, **kw) is _HostPath, kw
+        assert went(W2, resident=False, **kw) is _HostPath, kw
+
+    carried = ((W2, {}), (W2.astype(np.complex64), {}), (W3, {}),
+               (M, dict(integrator=qfa.magmp, hamiltonian=qfa.solve_mhd)))
+    for W, kw in carried:
+        assert went(W, resident=True, **kw) is _Resident, (W.shape, W.dtype)
+        assert went(W, **kw) is _Resident, (W.shape, W.dtype)
+        assert went(W, resident=False, **kw) is _HostPath, (W.shape, W.dtype)
