@@ -87,7 +87,9 @@ int qf_laplace(qf_ctx *ctx, const void *P_host, void *W_host);
 /* _solve_cpu(lap, W, P, ...) with a caller-supplied (N,N,2) coefficient table: the
  * solver underneath solve_heat / solve_helmholtz / solve_viscdamp (cpu.py:737-943).
  * The factorisation of `lap_host` is cached in the ctx under `table_key` (any
- * non-zero caller-chosen id; pass 0 to refactor on every call).
+ * non-zero caller-chosen id; pass 0 to refactor on every call).  The key must IDENTIFY
+ * the content: two tables that differ anywhere need two keys (an id of the parameters the
+ * table was built from, or a digest of all of its bytes).
  * W_host == P_host == NULL: the solve is applied to the context's resident state in place,
  * W <- T^-1 W, asynchronously -- a `strang_splitting` half step (solve_viscdamp with theta = 1,
  * isospectral.py:466-467, 598-599) between qf_isomp / qf_isomp_continue calls without PCIe. */
@@ -95,7 +97,10 @@ int qf_solve_tridiagonal(qf_ctx *ctx, const double *lap_host, unsigned long long
                          const void *W_host, void *P_host, int skewh);
 /* The factor cache is bounded: least-recently-used entries are recycled once
  * QUFLOW_HIP_FACTOR_CACHE_MB (default 512) of device memory is reached, and a key that returns
- * with a different table (fingerprint of 4096 sampled entries) is refactored.  Entries / bytes held: */
+ * with a different fingerprint is refactored.  The fingerprint is a safety net, not an identity: it
+ * reads 4096 strided doubles of the 2 N^2 (stride 2 N^2 / 4096: from N = 64 on only diagonal
+ * coefficients, never a coupling coefficient) plus the last one, and must not be relied on to tell
+ * two tables apart.  Entries / bytes held: */
 int qf_factor_cache_stats(qf_ctx *ctx, int *entries, unsigned long long *device_bytes);
 
 /* ---- the Hamiltonian of the flow.  Built in: P = Delta^-1 W.  Installed: P = T^-1 (W - F) with T any tridiagonal
@@ -109,7 +114,11 @@ int qf_factor_cache_stats(qf_ctx *ctx, int *entries, unsigned long long *device_
  *   offset_host N x N complex128, NULL = none.  Must be exactly skew-Hermitian: the solve reads its upper triangle only
  *               (the caller checks; quflow_amd.TridiagonalHamiltonian does).
  *   *_key       caller-chosen ids (0: always refactor / upload again).  A call that repeats the key AND the fingerprint
- *               (4096 sampled entries, as qf_solve_tridiagonal) of what the context still holds neither refactors nor uploads.
+ *               of what the context still holds neither refactors nor uploads, so each key must IDENTIFY its content: two
+ *               tables or two offsets that differ anywhere need two keys (quflow_amd.TridiagonalHamiltonian digests every
+ *               byte, once, when it is constructed).  The fingerprint, as in qf_solve_tridiagonal, reads 4096 strided
+ *               doubles plus the last one -- from N = 64 on real parts only of an offset, diagonal coefficients only of a
+ *               table -- and must not be relied on to tell contents apart.
  * Not followed (they keep the built-in solve): the complex64 entry points, the general (skewh = 0) branches, magmp,
  * qf_solve_poisson, qf_diagnostics / qf_isomp_diag (energy_euler stays the Euler energy -<W, Delta^-1 W>/2),
  * qf_scale_decomposition. */
@@ -139,8 +148,11 @@ int qf_hamiltonian_energy(qf_ctx *ctx, double *H);
  * the host-hook route, so a host callable that repeats the lines above gives the same trajectory bit for bit.
  *   F0_host   N x N complex128, NULL = none; kept in a buffer the context owns.  Meant to be skew-Hermitian (the caller
  *             checks; quflow_amd.AffineForcing does).
- *   F0_key    caller-chosen id (0: always upload again).  A call that repeats the key AND the fingerprint (4096 sampled
- *             entries) of what the context still holds does not upload again.
+ *   F0_key    caller-chosen id (0: always upload again).  A call that repeats the key AND the fingerprint of what the
+ *             context still holds does not upload again, so the key must IDENTIFY the pattern: two patterns that differ
+ *             anywhere need two keys (quflow_amd.AffineForcing digests every byte, once, when it is constructed).  The
+ *             fingerprint reads 4096 strided doubles plus the last one -- from N = 64 on real parts only -- and must not
+ *             be relied on to tell patterns apart.
  *   a_*       finite, else QF_ERR_INVALID.
  * FOLLOW an installed forcing: qf_isomp_forced; qf_isomp_hooked with k = 1, not magnetic, and qf_erk_hooked -- both when
  * their hook table has no `forcing` member (with one as well: QF_ERR_UNSUPPORTED); qf_forcing.

@@ -9,7 +9,7 @@ Everything below runs hand-written HIP kernels through the C ABI
 """
 import collections
 import ctypes
-import zlib
+import hashlib
 
 import numpy as np
 
@@ -318,13 +318,22 @@ def coriolis(N, omega):
     return F
 
 
-def _sample_key(tag, a):
-    """A 64-bit id of a host array for the library's caches: its shape and a CRC of up to 64 Ki entries spread over it
-    (the library's own fingerprint catches a key that comes back with other content)."""
-    flat = np.ascontiguousarray(a).reshape(-1).view(np.float64)
-    stride = max(1, flat.shape[0] // 65536)
-    crc = zlib.crc32(flat[::stride].tobytes()) ^ (zlib.crc32(flat[-1:].tobytes()) << 1)
-    return _table_key(tag, a.shape, int(crc))
+def _content_key(tag, a):
+    """A 64-bit id of a host array for the library's caches, from its WHOLE content: the tag, the dtype, the shape and every
+    byte (SHA-256, first 8 bytes; never 0, which the library reads as "always upload").  The library reuses what a context
+    holds when the key repeats, and its own fingerprint reads 4096 strided entries only: the key is what tells two contents
+    apart, so it must not sample.  One pass over the array: computed once, by the constructors, never per install."""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256(("%s|%s|%r|" % (tag, a.dtype.str, a.shape)).encode())
+    h.update(a.reshape(-1).view(np.uint8))
+    return int.from_bytes(h.digest()[:8], "little") or 1
+
+
+def _owned(a, dtype):
+    """A C-contiguous copy of `a` that nobody else holds, write-protected: what an immutable instance keeps and keys."""
+    a = np.array(a, dtype=dtype, order="C")
+    a.setflags(write=False)
+    return a
 
 
 class TridiagonalHamiltonian:
@@ -344,10 +353,14 @@ class TridiagonalHamiltonian:
     commutator, magmp) an instance is the callable `H(W) -> P` it also is and takes the foreign-Hamiltonian route.
 
     The offset must be EXACTLY skew-Hermitian (the skew-Hermitian solve reads the upper triangle of its right-hand side
-    only): ValueError otherwise."""
+    only): ValueError otherwise.
+
+    Instances are immutable: `table` and `offset` are write-protected copies of what was passed, and `table_key` /
+    `offset_key`, by which a context recognises what it already holds, are digests of their whole content, computed here
+    once.  A run that edits its topography makes a new instance."""
 
     def __init__(self, table, offset=None):
-        table = np.ascontiguousarray(table, dtype=np.float64)
+        table = _owned(table, np.float64)
         if table.ndim != 3 or table.shape[0] != table.shape[1] or table.shape[2] != 2 or table.shape[0] < 2:
             raise ValueError("table must be an (N,N,2) coefficient table, got shape %s" % (table.shape,))
         self.N = int(table.shape[0])
@@ -355,15 +368,25 @@ class TridiagonalHamiltonian:
         self.builtin = False         # the table is the built-in Laplacian's: the context's own factors serve
         self.offset = None
         if offset is not None:
-            offset = np.ascontiguousarray(offset, dtype=np.complex128)
+            offset = _owned(offset, np.complex128)
             if offset.shape != (self.N, self.N):
                 raise ValueError("offset must be (%d, %d), got %s" % (self.N, self.N, offset.shape))
             if not np.array_equal(offset, -offset.conj().T):
                 raise ValueError("offset must be exactly skew-Hermitian (F == -F^H entry by entry): project it with "
                                  "F = (F - F^H) / 2 first")
             self.offset = offset
-        self.table_key = _sample_key("ham_table", self.table)
-        self.offset_key = 0 if self.offset is None else _sample_key("ham_offset", self.offset)
+        # (the instance owns write-protected copies: the keys, computed here once from the whole content, stay true)
+        self.table_key = _content_key("ham_table", self.table)
+        self.offset_key = 0 if self.offset is None else _content_key("ham_offset", self.offset)
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        for a in (self.table, self.offset):       # (numpy unpickles arrays writeable)
+            if a is not None:
+                a.setflags(write=False)
+        # (keyed again, not trusted: a simulation stored by an earlier version carries keys of sampled entries)
+        self.table_key = _content_key("ham_table", self.table)
+        self.offset_key = 0 if self.offset is None else _content_key("ham_offset", self.offset)
 
     @classmethod
     def poisson(cls, N, offset=None):
@@ -487,7 +510,14 @@ class AffineForcing:
             F0.setflags(write=False)
             self.F0 = F0
             self.N = int(F0.shape[0])
-            self.F0_key = _sample_key("forcing_f0", F0)
+            self.F0_key = _content_key("forcing_f0", F0)
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        if self.F0 is not None:                   # (numpy unpickles arrays writeable)
+            self.F0.setflags(write=False)
+            # (keyed again, not trusted: a simulation stored by an earlier version carries a key of sampled entries)
+            self.F0_key = _content_key("forcing_f0", self.F0)
 
     def check_size(self, N):
         if self.N is not None and int(N) != self.N:

@@ -103,6 +103,127 @@ def test_check_size(qfa):
         g.check_size(N)
 
 
+# ----------------------------------------------------------------------------- the key identifies the content
+# The library reuses the pattern a context holds when F0_key and its own fingerprint both repeat, and the fingerprint reads
+# 4096 strided doubles (stride 2 N^2 / 4096: even from N = 64, so real parts only) plus the last one.  The key alone tells two
+# patterns apart.  N = 256, 257: the smallest sizes at which a key made of 65536 strided doubles skips entries as well (one a
+# multiple of 64, one ragged); 1024: strides 32 and 512.  Each perturbation keeps the matrix exactly skew-Hermitian.
+IDENTITY_SIZES = (256, 257, 1024)
+
+
+def perturb_imag_pair(X):
+    X[1, 2] += 0.5j
+    X[2, 1] += 0.5j
+
+
+def perturb_zonal(X):
+    X[5, 5] += 0.5j          # (an odd flat index of the interleaved doubles: no even stride visits it)
+
+
+def perturb_real_pair(X):
+    X[1, 2] += 0.5
+    X[2, 1] -= 0.5
+
+
+PERTURBATIONS = {"imag_pair": perturb_imag_pair, "zonal": perturb_zonal, "real_pair": perturb_real_pair}
+_BASE = {}
+
+
+def base_and_perturbed(N, name):
+    """(X, X perturbed): seeded, exactly skew-Hermitian, different in one entry or one mirrored pair."""
+    if N not in _BASE:
+        _BASE[N] = skew(N, 40)
+        _BASE[N].setflags(write=False)
+    X = _BASE[N]
+    G = X.copy()
+    PERTURBATIONS[name](G)
+    assert np.array_equal(G, -G.conj().T) and int(np.count_nonzero(G != X)) in (1, 2)
+    return X, G
+
+
+@pytest.mark.parametrize("name", sorted(PERTURBATIONS))
+@pytest.mark.parametrize("N", IDENTITY_SIZES)
+def test_f0_key_tells_patterns_apart(qfa, N, name):
+    X, G = base_and_perturbed(N, name)
+    fx, fg = qfa.AffineForcing(X), qfa.AffineForcing(G)
+    assert fx.F0_key != fg.F0_key, (N, name)
+    assert fx.F0_key != 0 and fg.F0_key != 0
+    # equal content, built twice (from another array object, and with other coefficients): the same key
+    assert qfa.AffineForcing(X.copy(), a_W=-0.5).F0_key == fx.F0_key
+    assert qfa.AffineForcing(np.asfortranarray(G)).F0_key == fg.F0_key
+
+
+def test_f0_key_covers_shape_and_tag(qfa):
+    from quflow_amd import laplacian as lap
+    a = np.zeros((4, 4), dtype=np.complex128)
+    assert lap._content_key("forcing_f0", a) != lap._content_key("ham_offset", a)
+    assert lap._content_key("forcing_f0", a) != lap._content_key("forcing_f0", a.reshape(2, 8))
+    assert lap._content_key("forcing_f0", a) != lap._content_key("forcing_f0", a.view(np.float64))
+    assert all(0 < lap._content_key("t", np.full(3, v)) < 2 ** 64 for v in range(64))
+
+
+class StubContext:
+    """What install() needs of a context, without a device: the size, a handle, and a library whose entry points record
+    their arguments and succeed."""
+
+    def __init__(self, N):
+        import ctypes
+        self.N, self.handle, self.calls = N, ctypes.c_void_p(1), []
+        self._lib = self
+
+    def __getattr__(self, name):
+        if not name.startswith("qf_"):
+            raise AttributeError(name)
+
+        def entry(*args):
+            self.calls.append((name, args))
+            return 0
+        return entry
+
+
+def counted_digest(monkeypatch):
+    """quflow_amd.laplacian._content_key with a counter in front: [(tag, shape), ...] of every call."""
+    from quflow_amd import laplacian as lap
+    seen = []
+    real = lap._content_key
+
+    def counting(tag, a):
+        seen.append((tag, np.shape(a)))
+        return real(tag, a)
+    monkeypatch.setattr(lap, "_content_key", counting)
+    return seen
+
+
+def test_key_is_computed_once_and_install_does_not_hash(qfa, monkeypatch):
+    N = 256
+    X, _ = base_and_perturbed(N, "zonal")
+    seen = counted_digest(monkeypatch)
+    f = qfa.AffineForcing(X, a_W=-0.01)
+    assert seen == [("forcing_f0", (N, N))]
+    qfa.AffineForcing(a_W=-0.01)                       # no pattern: nothing to key
+    assert len(seen) == 1
+    ctx = StubContext(N)
+    for _ in range(3):
+        f.install(ctx)
+        f.uninstall(ctx)
+    assert len(seen) == 1, seen
+    sets = [args for name, args in ctx.calls if name == "qf_set_forcing"]
+    assert len(sets) == 3 and all(a[1].value == f.F0.ctypes.data and a[2].value == f.F0_key for a in sets)
+    assert [name for name, _ in ctx.calls].count("qf_clear_forcing") == 3
+
+
+def test_pattern_stays_write_protected_through_pickle(qfa):
+    import pickle
+    f = qfa.AffineForcing(skew(8, 0), a_W=-0.01)
+    g = pickle.loads(pickle.dumps(f))
+    assert np.array_equal(g.F0, f.F0) and g.F0_key == f.F0_key and not g.F0.flags.writeable
+    assert pickle.loads(pickle.dumps(qfa.AffineForcing(a_P=1.0))).F0 is None
+    # a stored instance is keyed again from its content: one written with a key of sampled entries does not bring it back
+    old = qfa.AffineForcing(skew(8, 0))
+    old.F0_key = 12345
+    assert pickle.loads(pickle.dumps(old)).F0_key == f.F0_key
+
+
 # ----------------------------------------------------------------------------- what solve keeps on the device
 def test_resident_kind_of_forced_runs(qfa):
     from quflow_amd import simulation

@@ -131,6 +131,130 @@ def test_instances_pickle(host_tables):
         assert (H2.table_key, H2.offset_key) == (H.table_key, H.offset_key)
 
 
+# ----------------------------------------------------------------------------- the keys identify the content
+# The library reuses the factors and the offset a context holds when the key and its own fingerprint both repeat, and the
+# fingerprint reads 4096 strided doubles -- from N = 64 an even stride: real parts of an offset, the diagonal column of a
+# table -- plus the last one.  The keys alone tell two contents apart (sizes and offset perturbations: test_forcing_host.py).
+def coupling_perturbed(table, factor=1.5):
+    """A copy of an (N,N,2) table with ONE coupling coefficient changed: entry (2, 3) of the second column -- it ties P[2,3] to
+    P[1,2] on the first superdiagonal -- and its partner (3, 2), which the layout of laplacian(N) keeps equal to it."""
+    T = np.array(table)
+    assert T[2, 3, 1] != 0.0 and T[2, 3, 1] == T[3, 2, 1]
+    T[2, 3, 1] *= factor
+    T[3, 2, 1] *= factor
+    return T
+
+
+_ONES = {}
+
+
+def ones_table(N):
+    if N not in _ONES:
+        _ONES[N] = np.ones((N, N, 2))
+        _ONES[N].setflags(write=False)
+    return _ONES[N]
+
+
+@pytest.mark.parametrize("name", ["imag_pair", "real_pair", "zonal"])
+@pytest.mark.parametrize("N", [256, 257, 1024])
+def test_offset_key_tells_offsets_apart(N, name):
+    from quflow_amd import laplacian as lap
+    from test_forcing_host import base_and_perturbed
+    X, G = base_and_perturbed(N, name)
+    tab = ones_table(N)                                  # (any table: nothing is solved here)
+    hx, hg = lap.TridiagonalHamiltonian(tab, offset=X), lap.TridiagonalHamiltonian(tab, offset=G)
+    assert hx.offset_key != hg.offset_key, (N, name)
+    assert hx.offset_key != 0 and hg.offset_key != 0 and hx.table_key == hg.table_key
+    # equal content, built twice: the same keys
+    h2 = lap.TridiagonalHamiltonian(tab.copy(), offset=X.copy())
+    assert (h2.table_key, h2.offset_key) == (hx.table_key, hx.offset_key)
+    # the same matrix as a forcing pattern is another cache's content
+    assert lap.AffineForcing(X).F0_key != hx.offset_key
+
+
+@pytest.mark.parametrize("N", [256, 257, 1024])
+def test_table_key_tells_tables_apart(host_tables, N):
+    lap = host_tables
+    S = lap.TridiagonalHamiltonian.shifted(N, -0.5, -1.0)
+    T = coupling_perturbed(S.table)
+    assert int(np.count_nonzero(T != S.table)) == 2 and np.array_equal(T[:, :, 0], S.table[:, :, 0])
+    P = lap.TridiagonalHamiltonian(T)
+    assert P.table_key != S.table_key, N
+    assert lap.TridiagonalHamiltonian(T.copy()).table_key == P.table_key
+    assert lap.TridiagonalHamiltonian.shifted(N, -0.5, -1.0).table_key == S.table_key
+    assert P.offset_key == 0 and S.offset_key == 0
+
+
+def test_keys_are_computed_once_and_install_does_not_hash(host_tables, monkeypatch):
+    from test_forcing_host import StubContext, base_and_perturbed, counted_digest
+    lap = host_tables
+    N = 256
+    X, _ = base_and_perturbed(N, "zonal")
+    seen = counted_digest(monkeypatch)
+    H = lap.TridiagonalHamiltonian(ones_table(N), offset=X)
+    assert seen == [("ham_table", (N, N, 2)), ("ham_offset", (N, N))]
+    made = [H, lap.TridiagonalHamiltonian.poisson(N), lap.TridiagonalHamiltonian.globalqg(N, 2.0),
+            lap.TridiagonalHamiltonian.shifted(N, -0.5, -1.0), lap.TridiagonalHamiltonian.poisson(N, offset=X)]
+    assert [tag for tag, _ in seen[2:]] == ["ham_table", "ham_table", "ham_table", "ham_table", "ham_offset"]
+    ctx = StubContext(N)
+    for h in made:
+        for _ in range(2):
+            h.install(ctx)
+            h.uninstall(ctx)
+    assert len(seen) == 7, seen
+    sets = [args for name, args in ctx.calls if name == "qf_set_hamiltonian"]
+    assert len(sets) == 10 and [name for name, _ in ctx.calls].count("qf_clear_hamiltonian") == 10
+    for h, a in zip([h for h in made for _ in range(2)], sets):
+        assert (a[1] is None) == h.builtin and (a[3] is None) == (h.offset is None)
+        assert h.builtin or a[1].value == h.table.ctypes.data
+        assert a[2].value == h.table_key and a[4].value == h.offset_key
+        assert h.offset is None or a[3].value == h.offset.ctypes.data
+
+
+def test_instance_owns_its_arrays(host_tables):
+    from test_forcing_host import base_and_perturbed
+    lap = host_tables
+    N = 256
+    X, _ = base_and_perturbed(N, "zonal")
+    for tab, off in ((np.array(lap._shifted_table(N, -0.5, -1.0)), X.copy()),                   # contiguous, right dtype
+                     (np.asfortranarray(lap._shifted_table(N, -0.5, -1.0)), np.asfortranarray(X))):
+        tab0, off0 = tab.copy(), off.copy()
+        H = lap.TridiagonalHamiltonian(tab, offset=off)
+        keys = (H.table_key, H.offset_key)
+        assert not np.shares_memory(H.table, tab) and not np.shares_memory(H.offset, off)
+        assert H.table.flags.c_contiguous and H.offset.flags.c_contiguous
+        assert not H.table.flags.writeable and not H.offset.flags.writeable
+        # the caller goes on with its arrays: a topography edit, another coupling
+        tab[2, 3, 1] *= 1.5
+        tab[3, 2, 1] *= 1.5
+        off[5, 5] += 0.5j
+        assert np.array_equal(H.table, tab0) and np.array_equal(H.offset, off0)
+        assert (H.table_key, H.offset_key) == keys
+        fresh = lap.TridiagonalHamiltonian(tab0, offset=off0)
+        assert (fresh.table_key, fresh.offset_key) == keys
+        edited = lap.TridiagonalHamiltonian(tab, offset=off)
+        assert edited.table_key != keys[0] and edited.offset_key != keys[1]
+        with pytest.raises(ValueError):
+            H.table[2, 3, 1] = 0.0
+        with pytest.raises(ValueError):
+            H.offset[5, 5] = 0.0
+    # the classmethods go through the constructor: an instance never holds the module's cached table
+    S = lap.TridiagonalHamiltonian.shifted(N, -0.5, -1.0)
+    G = lap.TridiagonalHamiltonian.globalqg(N, 2.0)
+    assert not np.shares_memory(S.table, lap._shifted_table(N, -0.5, -1.0)) and not S.table.flags.writeable
+    assert not np.shares_memory(G.table, lap._globalqg_table(N, 2.0)) and not G.table.flags.writeable
+    assert lap._shifted_table(N, -0.5, -1.0).flags.writeable          # (the cache's own array is left as it was)
+    # ... and a pickled instance comes back write-protected, with its keys
+    H1 = lap.TridiagonalHamiltonian.poisson(N, offset=X)
+    keys = (H1.table_key, H1.offset_key)
+    H2 = pickle.loads(pickle.dumps(H1))
+    assert H2.builtin and not H2.table.flags.writeable and not H2.offset.flags.writeable
+    # ... keyed again from its content: one stored with keys of sampled entries does not bring them back
+    H1.table_key, H1.offset_key = 12345, 6789
+    H3 = pickle.loads(pickle.dumps(H1))
+    assert (H2.table_key, H2.offset_key) == keys and (H3.table_key, H3.offset_key) == keys
+
+
 def test_argument_errors(host_tables):
     lap = host_tables
     N = 12

@@ -297,6 +297,11 @@ def test_installed_hamiltonian_does_not_leak(qfa, oracle):
 
 
 # ----------------------------------------------------------------------------- evaluation and energy
+def evaluation_bar(N, Pc):
+    """The bar of one evaluation H(W) against the oracle's solve Pc: 1e-12 N max|Pc|."""
+    return 1e-12 * N * float(np.abs(Pc).max())
+
+
 @pytest.mark.parametrize("N", [63, 1025])
 @pytest.mark.parametrize("case", ["A", "B"])
 def test_evaluation_vs_oracle(qfa, oracle, case, N):
@@ -304,7 +309,7 @@ def test_evaluation_vs_oracle(qfa, oracle, case, N):
     W = white(oracle, N)
     Pc = f(W)
     Pg = H(W)
-    bar = 1e-12 * N * float(np.abs(Pc).max())
+    bar = evaluation_bar(N, Pc)
     err = report("H(W) %s N=%d" % (case, N), maxabs(Pg, Pc), bar)
     assert err <= bar
     assert np.array_equal(Pg, -Pg.conj().T)
