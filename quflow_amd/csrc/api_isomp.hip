@@ -164,12 +164,12 @@ int select_second_product(qf_ctx *ctx)
     return QF_OK;
 }
 
-// complex64: the upper-triangle second product (k_cgemm_tri) for an exactly skew-Hermitian state, fused protocol only
+// complex64: the upper-triangle second product (k_cgemm_tri32) for an exactly skew-Hermitian state, fused protocol only
 int select_second_product_c64(qf_ctx *ctx)
 {
     qf_c64 *f = ctx->c64;
     f->tri = false;
-    if (f->tri_allowed && ctx->gemm_tri_allowed && (qf_c64_tile(ctx) == 32 || ctx->N % 64 == 0) && ctx->N >= 64) {      // (QUFLOW_HIP_GEMM2=full: A/B)
+    if (f->tri_allowed && ctx->gemm_tri_allowed && ctx->N >= 64) {      // (QUFLOW_HIP_GEMM2=full: A/B)
         QF_TRY(check_skew(ctx, f));
         if (f->w_skew_known) {
             QF_TRY(qf_c64_tri_alloc(ctx));
@@ -967,11 +967,10 @@ int c64_fixedpoint_products(const char *name, bool tri, qf_ctx *ctx, const void 
     if (tri) {
         QF_TRY(qf_launch_cgemm_tri(ctx, f->PW, f->Phalf, &ep));
         QF_TRY(qf_launch_mirror_lower(ctx, f->dW[1]));
-        QF_TRY(qf_launch_sum_rowpart(ctx, f->rowpart, (N + qf_c64_tile(ctx) - 1) / qf_c64_tile(ctx), ctx->rowsum));
     } else {
         QF_TRY(qf_launch_cgemm(ctx, f->PW, f->Phalf, nullptr, &ep));
-        QF_TRY(qf_launch_sum_rowpart(ctx, f->rowpart, f->rowpart_tiles, ctx->rowsum));
     }
+    QF_TRY(qf_launch_sum_rowpart(ctx, f->rowpart, f->rowpart_tiles, ctx->rowsum));      // (both forms: column tiles of QF_C64_TILE)
     QF_HIP(hipMemcpyAsync(dW_new_host, f->dW[1], bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipMemcpyAsync(Whalf_new_host, f->Whalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipMemcpyAsync(rowsum_host, ctx->rowsum, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -245,13 +245,13 @@ struct qf_c64 {
     float2 *stage = nullptr;                   // staging of the host-in / host-out entry points
     float *lap = nullptr;                      // (N,N,2) float32 coefficient table of the Poisson problem (cpu.py:725)
     float2 *tab = nullptr;                     // its factorisation {w, 1/b'} in float32
-    double *rowpart = nullptr;                 // [column tiles of 64][N] partial row sums of the second product
+    double *rowpart = nullptr;                 // [column tiles of QF_C64_TILE][N] partial row sums of the second product
     int rowpart_tiles = 0;
     int dw_cur = 0;
     bool increment_is_zero = true;             // (as qf_ctx's)
     bool increment_valid = false;
     float2 *W2 = nullptr, *Whalf2 = nullptr;   // fused step end: second buffers of the W / Whalf pairs (on demand)
-    // upper-triangle second product (k_cgemm_tri): exchange area [tiles][4][64*64], arrival counters [tiles], K pieces
+    // upper-triangle second product (k_cgemm_tri32): exchange area [tiles][4][32*32], arrival counters [tiles], K pieces
     // per off-diagonal / diagonal tile; `tri` = selected for the running call (W exactly skew-Hermitian)
     float2 *tri_partial = nullptr;
     unsigned *tri_arrive = nullptr;
@@ -584,11 +584,11 @@ int qf_launch_laplace(qf_ctx *ctx, const float2 *P, float2 *W);
 int qf_c64_alloc(qf_ctx *ctx);
 void qf_c64_free(qf_c64 *f);
 int qf_launch_cgemm(qf_ctx *ctx, const float2 *A, const float2 *B, float2 *C, const qf_epilogue_f *ep, qf_guard guard = qf_guard());
-// tile size (32 or 64) of the complex64 second product (and of the row-sum slots it fills): k_cgemm32<EPI> / k_cgemm_tri32 or
-// k_cgemm<EPI> / k_cgemm_tri; and of the plain first product: k_cgemm32 or k_cgemm / k_cgemm_ks
-int qf_c64_tile(const qf_ctx *ctx);
+// tile size of the complex64 second product, full (k_cgemm<32, true, ..>) and upper-triangle (k_cgemm_tri32), and of the
+// row-sum slots it fills: 32 at every N.  The plain first product takes 32 or 64 (k_cgemm<32 / 64, false, ..>) by size.
+constexpr int QF_C64_TILE = 32;
 int qf_c64_tile_first(const qf_ctx *ctx);
-// the second product on the upper triangle of 64x64 tiles (requires N % 64 == 0 and qf_c64_tri_alloc)
+// the second product on the upper triangle of 32 x 32 tiles (requires N >= 64 and qf_c64_tri_alloc; edge tiles guarded)
 int qf_c64_tri_alloc(qf_ctx *ctx);
 int qf_launch_cgemm_tri(qf_ctx *ctx, const float2 *A, const float2 *B, const qf_epilogue_f *ep, qf_guard guard = qf_guard());
 

@@ -6,13 +6,14 @@
 // from the float32 machine epsilon (isospectral.py:440-448).  This file holds the float32 kernels that are not
 // instantiations of the double-precision ones (poisson.hip instantiates the solve for float, elementwise.hip the end-of-step
 // update, the infinity norm, the diagnostics' inner products and the skew-Hermitian check for float2):
-//   * k_cgemm / k_cgemm32: complex64 N x N x N product on the fp32 matrix cores (v_mfma_f32_32x32x2_f32 / 16x16x4: exact
-//     f32 fma chains at 64 flop/clk/SIMD = 157.3 TFLOP/s, MI355X_MICROARCH.md), 3M form like the fp64 kernel, with the
-//     fused epilogue of the second product (isospectral.py:499-509, 481-482, 526-534) and the fused step end;
-//     k_cgemm_ks / k_cgemm32<.., KS>: the plain product with the K range cut between groups of wavefronts of one
-//     workgroup (launches with one tile per CU);
-//   * k_cgemm_tri / k_cgemm_tri32: the second product on the upper triangle only (skew-Hermitian state), K pieces per
+//   * k_cgemm<TILE, EPI, EXACT, KS>: complex64 N x N x N product on the fp32 matrix cores (v_mfma_f32_32x32x2_f32 on
+//     64 x 64 block tiles, 16x16x4 on 32 x 32: exact f32 fma chains at 64 flop/clk/SIMD = 157.3 TFLOP/s,
+//     MI355X_MICROARCH.md), 3M form like the fp64 kernel.  EPI: the fused epilogue of the second product
+//     (isospectral.py:499-509, 481-482, 526-534) and the fused step end, on 32 x 32 tiles only.  KS > 1: the plain product
+//     with the K range cut between KS groups of wavefronts of one workgroup (launches with one tile per CU);
+//   * k_cgemm_tri32: the second product on the upper triangle only (skew-Hermitian state), 32 x 32 tiles, K pieces per
 //     tile exchanged through memory, the last arrival combines and runs the epilogue for the tile and its mirror image.
+// The K loop (cg_k_loop) and the epilogue's arithmetic (cg_stage_pw_mirror, cg_epilogue_entry) are written once for all of them.
 // The control plane is shared with the double-precision path: tagged launches, device-side exit decision on double row
 // sums (in the second product's last tile, qf_step_end.h; k_norm_decide in the two-kernel protocol), progress record --
 // see api_isomp.hip.
@@ -22,6 +23,7 @@
 #pragma clang fp contract(off)  // the epilogues' elementwise arithmetic is the reference's: not re-associated or fused
 
 typedef float v16f __attribute__((ext_vector_type(16)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -44,30 +46,57 @@ __device__ __forceinline__ float4 ld4(const float2 *p)
     }
 }
 
-constexpr int CBM = 64, CBN = 64, CBK = 16;       // block tile (complex entries)
-constexpr int SA = CBM + 1;                       // k-major A image: row stride padded by one entry (transposing
+// the entries (or zeros) at row gr, columns gc and gc + 1 of an N x N matrix, gc = c0 + c1: the guarded form of ld4.
+// (The column comes in two parts, the tile's or K-tile's origin and the lane's offset, and both are added to the address
+// in 64 bits: the uniform part then stays in scalar registers and the lane's part outside the K loop.)
+template <bool EXACT>
+__device__ __forceinline__ float4 ld4_guarded(const float2 *__restrict__ M, int N, int gr, int c0, int c1)
+{
+    const int gc = c0 + c1;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (EXACT || (gr < N && gc + 1 < N)) v = ld4<EXACT>(M + (size_t)gr * N + c0 + c1);
+    else if (gr < N && gc < N) { const float2 t = M[(size_t)gr * N + c0 + c1]; v = make_float4(t.x, t.y, 0.f, 0.f); }
+    return v;
+}
+
+// ---- block tiles.  A workgroup (or each of its K groups) is 4 wavefronts (2 x 2), one MF x MF MFMA tile each; K-tiles
+// of CBK complex entries.  MFMA lane maps (cdna_hip_programming.md section 3), lm = lane % MF, lk = lane / MF:
+// A[i = lm][k = lk], B[k = lk][j = lm], C/D[row = (reg & 3) + 8 (reg >> 2) + 4 lk][col = lm] -- f32 32x32x2: 16
+// accumulator registers, two k per instruction; f32 16x16x4: 4 registers (row = 4 lk + reg), four k.
+// The B image is row-major [CBK][BN] for both.  The two A images differ on purpose (a_at).
+constexpr int CBK = 16;
+template <int TILE> struct cg_tile;
+template <> struct cg_tile<64> {
+    typedef v16f acc;
+    static constexpr int BM = 64, BN = 64, MF = 32, KM = 2, Q = 16;
+    static constexpr int SA = BM + 1;             // k-major A image: row stride padded by one entry (transposing
                                                   // ds_write_b64 of 8 k-pairs x 2 rows: 16 distinct 8-byte slots)
-constexpr int SB = CBN;
-constexpr int A_BYTES = CBK * SA * (int)sizeof(float2);
-constexpr int B_BYTES = CBK * SB * (int)sizeof(float2);
-constexpr int CG_MAIN_BYTES = 2 * (A_BYTES + B_BYTES);
+    static constexpr int A_BYTES = CBK * SA * (int)sizeof(float2);
+    static constexpr int B_BYTES = CBK * BN * (int)sizeof(float2);
+    static constexpr int MAIN_BYTES = 2 * (A_BYTES + B_BYTES);      // double-buffered
+    static __device__ __forceinline__ int a_at(int i, int k) { return k * SA + i; }
+    static __device__ __forceinline__ acc mfma(float a, float b, acc c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+};
 // below N = 768 a 64 x 64 tiling leaves most CUs without a workgroup (64 tiles at N = 512): 32 x 32 block tiles
 // there, one 16 x 16 MFMA tile (v_mfma_f32_16x16x4_f32) per wavefront.  Its A image stays row-major with an odd
 // row stride: the fragment read of lane (i = l & 15, k = l >> 4) then hits 32 distinct bank pairs per lane group
 // (34 i mod 64 are sixteen distinct even banks, the k-neighbours sit two banks further), and so do the staging
 // writes (rows r, r+1 x eight k-pairs).
-constexpr int SBM = 32, SBN = 32;
-constexpr int SAK = CBK + 1;                      // row stride (complex entries) of the small tile's row-major A image
-constexpr int SA_BYTES = SBM * SAK * (int)sizeof(float2);
-constexpr int SB_BYTES = CBK * SBN * (int)sizeof(float2);
-constexpr int TT = CBN + 1;                       // row stride of the mirrored PW tile staged for the epilogue
-constexpr int CG_EPI_BYTES = CBM * TT * (int)sizeof(float2) + (2 * CBM + 16) * (int)sizeof(double);
-constexpr int CG_SMEM = CG_MAIN_BYTES > CG_EPI_BYTES ? CG_MAIN_BYTES : CG_EPI_BYTES;
-constexpr int STT = SBN + 1;
-constexpr int SG_MAIN_BYTES = 2 * (SA_BYTES + SB_BYTES);
-constexpr int SG_EPI_BYTES = SBM * STT * (int)sizeof(float2) + (2 * SBM + 16) * (int)sizeof(double);
-constexpr int SG_SMEM = SG_MAIN_BYTES > SG_EPI_BYTES ? SG_MAIN_BYTES : SG_EPI_BYTES;
-typedef float v4f __attribute__((ext_vector_type(4)));
+template <> struct cg_tile<32> {
+    typedef v4f acc;
+    static constexpr int BM = 32, BN = 32, MF = 16, KM = 4, Q = 4;
+    static constexpr int SAK = CBK + 1;           // row stride (complex entries) of the row-major A image
+    static constexpr int A_BYTES = BM * SAK * (int)sizeof(float2);
+    static constexpr int B_BYTES = CBK * BN * (int)sizeof(float2);
+    static constexpr int MAIN_BYTES = 2 * (A_BYTES + B_BYTES);
+    static constexpr int TT = BN + 1;             // row stride of the mirrored PW tile staged for the epilogue
+    static constexpr int TT_BYTES = BM * TT * (int)sizeof(float2);
+    static constexpr int EPI_BYTES = TT_BYTES + (2 * BM + 16) * (int)sizeof(double);      // + row sums [2][BM] + step end
+    static __device__ __forceinline__ int a_at(int i, int k) { return i * SAK + k; }
+    static __device__ __forceinline__ acc mfma(float a, float b, acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+};
+typedef cg_tile<QF_C64_TILE> cg_small;            // the second product's tile
+static_assert(cg_small::EPI_BYTES <= cg_small::MAIN_BYTES, "the square epilogue reuses the K loop's LDS");
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg)
 {
@@ -75,256 +104,77 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg)
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
 }
 
-// C = A @ B (EPI = false) or the second product with its fused epilogue (EPI = true):
-//   dW_new = A @ B + (PW - PW^H);  Whalf = W + dW_new;  rowpart[tile column][i] = sum_j |dW_old - dW_new|
-// 64 x 64 block tile, 4 wavefronts (2 x 2), one 32 x 32 MFMA tile each; K-tiles of 16 complex entries double-buffered
-// in LDS, two K-tiles in flight global -> registers.  3M: T1 = sum ar br, T2 = sum ai bi, T3 = sum (ar+ai)(br+bi).
-// MFMA f32 32x32x2 lane maps (cdna_hip_programming.md section 3): A[i = lane & 31][k = lane >> 5],
-// B[k = lane >> 5][j = lane & 31], C/D[row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)][col = lane & 31].
-template <bool EPI, bool EXACT>
-__global__ __launch_bounds__(256) void k_cgemm(int N, int tiles_n, const float2 *__restrict__ A, const float2 *__restrict__ B,
-                                               float2 *__restrict__ C, qf_epilogue_f ep, qf_guard guard)
+// The K loop of every complex64 product: the 3M sums (T1 = sum ar br, T2 = sum ai bi, T3 = sum (ar+ai)(br+bi)) of tile
+// (i0, j0) over the K-tiles kb .. kb + KTp - 1, run by the 256 threads of one K group on the group's LDS
+// (cg_tile<TILE>::MAIN_BYTES at `smem`).  K-tiles double-buffered in LDS, two K-tiles in flight global -> registers.
+// The barriers are the workgroup's: all K groups of one workgroup pass the same KTp.
+// EXACT = false: loads guarded, out-of-range operands are zeros (they add nothing to the products).
+// Staging maps: A rows tid / 8 (+ 32 for the second load of a 64-row tile), k-pair tid % 8;  B k-rows tid / (BN / 2)
+// (+ 8 likewise), column pair tid % (BN / 2).
+// (The accumulators are the loop's own and come back by value.  Taken by reference from the kernel, the MFMAs of the
+// 32 x 32 kernels no longer accumulated in place -- the three accumulators rotated through eight more registers, 66-70
+// VGPRs for 58-62, seven wavefronts per SIMD for eight.)
+template <int TILE> struct cg_acc3 { typename cg_tile<TILE>::acc t1, t2, t3; };
+template <int TILE, bool EXACT>
+__device__ __forceinline__ cg_acc3<TILE> cg_k_loop(const float2 *__restrict__ A, const float2 *__restrict__ B, int N, int i0, int j0, int kb,
+                                                   int KTp, unsigned char *smem)
 {
-    if (!qf_guard_iter(guard)) return;
-    // fused step end: the first product of a step's first iteration takes the Whalf prepared for it
-    if (!EPI && guard.alt && guard.state->wh_sel) B = static_cast<const float2 *>(guard.alt);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    typedef cg_tile<TILE> T;
+    typename T::acc t1, t2, t3;
+#pragma unroll
+    for (int q = 0; q < T::Q; ++q) { t1[q] = 0.f; t2[q] = 0.f; t3[q] = 0.f; }
+    constexpr int R = TILE / 32;                  // 16-byte loads per thread, operand and K-tile
+    constexpr int JP = T::BN / 2;                 // column pairs of a B row
+    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tm = lid / tiles_n, tn = lid % tiles_n;
-    const int i0 = tm * CBM, j0 = tn * CBN;
-    const int parity = (EPI && guard.state) ? guard.state->dw_parity : 0;
-    const float2 *__restrict__ dW_old = ep.dW[parity];
-    float2 *__restrict__ dW_new = ep.dW[parity ^ 1];
-    // fused step end: the state is Wpair[w_parity]; the candidate next state goes to the other buffer
-    const int wpar = (EPI && ep.fused && guard.state) ? guard.state->w_parity : 0;
-    const float2 *__restrict__ ep_W = (EPI && ep.fused) ? ep.Wpair[wpar] : ep.W;
-    float2 *__restrict__ ep_Wnext = (EPI && ep.fused) ? ep.Wpair[wpar ^ 1] : nullptr;
-
-    // staging maps: A rows (tid / 8) and + 32, k-pair tid % 8;  B k-rows (tid / 32) and + 8, column pair tid % 32
+    const int lm = lane % T::MF, lk = lane / T::MF;
     const int a_row = tid >> 3, a_kp = tid & 7;
-    const int b_k = tid >> 5, b_jp = tid & 31;
-    float4 ra[2][2], rb[2][2];
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int b_k = tid / JP, b_jp = tid % JP;
+    float4 ra[2][R], rb[2][R];
 
-    auto load_tile = [&](int kt, float4 (&a)[2], float4 (&b)[2]) {
-        const int k0 = kt * CBK;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int gi = i0 + a_row + 32 * r, gk = k0 + 2 * a_kp;
-            a[r] = zero4;
-            if (EXACT || (gi < N && gk + 1 < N)) a[r] = ld4<EXACT>(A + (size_t)gi * N + gk);
-            else if (gi < N && gk < N) { const float2 t = A[(size_t)gi * N + gk]; a[r] = make_float4(t.x, t.y, 0.f, 0.f); }
-            const int gkb = k0 + b_k + 8 * r, gj = j0 + 2 * b_jp;
-            b[r] = zero4;
-            if (EXACT || (gkb < N && gj + 1 < N)) b[r] = ld4<EXACT>(B + (size_t)gkb * N + gj);
-            else if (gkb < N && gj < N) { const float2 t = B[(size_t)gkb * N + gj]; b[r] = make_float4(t.x, t.y, 0.f, 0.f); }
-        }
-    };
-    auto store_tile = [&](int buf, const float4 (&a)[2], const float4 (&b)[2]) {
-        float2 *As = reinterpret_cast<float2 *>(smem + buf * A_BYTES);
-        float2 *Bs = reinterpret_cast<float2 *>(smem + 2 * A_BYTES + buf * B_BYTES);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            As[(2 * a_kp) * SA + a_row + 32 * r] = make_float2(a[r].x, a[r].y);
-            As[(2 * a_kp + 1) * SA + a_row + 32 * r] = make_float2(a[r].z, a[r].w);
-            *reinterpret_cast<float4 *>(Bs + (b_k + 8 * r) * SB + 2 * b_jp) = b[r];
-        }
-    };
-
-    v16f t1, t2, t3;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { t1[q] = 0.f; t2[q] = 0.f; t3[q] = 0.f; }
-
-    auto compute = [&](int buf) {
-        const float2 *As = reinterpret_cast<const float2 *>(smem + buf * A_BYTES) + wm * 32 + l31;
-        const float2 *Bs = reinterpret_cast<const float2 *>(smem + 2 * A_BYTES + buf * B_BYTES) + wn * 32 + l31;
-#pragma unroll
-        for (int s = 0; s < CBK / 2; ++s) {
-            const float2 a = As[(2 * s + lh) * SA];
-            const float2 b = Bs[(2 * s + lh) * SB];
-            t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, t1, 0, 0, 0);
-            t2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, t2, 0, 0, 0);
-            t3 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x + a.y, b.x + b.y, t3, 0, 0, 0);
-        }
-    };
-
-    const int KT = (N + CBK - 1) / CBK;
-    load_tile(0, ra[0], rb[0]);
-    if (KT > 1) load_tile(1, ra[1], rb[1]);
-    store_tile(0, ra[0], rb[0]);
-    __syncthreads();
-    if (KT > 2) load_tile(2, ra[0], rb[0]);
-    int kt = 0;
-    // two K-tiles per trip: LDS buffer and register-set indices are literals.  (Staging K-tile kt+1 and issuing
-    // the loads of kt+3 AHEAD of K-tile kt's MFMAs instead of behind them measured slower: 81.9 against 78.5 us
-    // at N=1024, 456 against 437 at N=2048 -- the waves then meet the LDS store path all at once.)
-    for (; kt + 1 < KT; kt += 2) {
-        compute(0);
-        store_tile(1, ra[1], rb[1]);                       // K-tile kt+1 (arrived two K-tiles ago)
-        if (kt + 3 < KT) load_tile(kt + 3, ra[1], rb[1]);
-        __syncthreads();
-        compute(1);
-        if (kt + 2 < KT) {
-            store_tile(0, ra[0], rb[0]);
-            if (kt + 4 < KT) load_tile(kt + 4, ra[0], rb[0]);
-        }
-        __syncthreads();
-    }
-    if (kt < KT) compute(0);
-
-    if constexpr (!EPI) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int gi = i0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-            const int gj = j0 + wn * 32 + l31;
-            if (EXACT || (gi < N && gj < N)) C[(size_t)gi * N + gj] = make_float2(t1[q] - t2[q], (t3[q] - t1[q]) - t2[q]);
-        }
-    } else {
-        // ---- fused epilogue.  The mirrored PW tile (rows j0.., columns i0..) goes through LDS so that both
-        // global reads of PW are row-coalesced; conj_subtract_ (isospectral.py:71-74): PW[i,j] - conj(PW[j,i]).
-        __syncthreads();      // every wave is done with the K-loop buffers
-        float2 *Tt = reinterpret_cast<float2 *>(smem);
-        double *rs = reinterpret_cast<double *>(smem + CBM * TT * sizeof(float2));   // [2][CBM]
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int row = (tid >> 5) + 8 * r, cp = tid & 31;
-            const int gj = j0 + row, gi = i0 + 2 * cp;
-            float4 v = zero4;
-            if (EXACT || (gj < N && gi + 1 < N)) v = ld4<EXACT>(ep.PW + (size_t)gj * N + gi);
-            else if (gj < N && gi < N) { const float2 t = ep.PW[(size_t)gj * N + gi]; v = make_float4(t.x, t.y, 0.f, 0.f); }
-            Tt[row * TT + 2 * cp] = make_float2(v.x, v.y);
-            Tt[row * TT + 2 * cp + 1] = make_float2(v.z, v.w);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int li = wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-            const int lj = wn * 32 + l31;
-            const int gi = i0 + li, gj = j0 + lj;
-            float a = 0.f;
-            if (EXACT || (gi < N && gj < N)) {
-                const size_t e = (size_t)gi * N + gj;
-                const float2 pw = ep.PW[e];
-                const float2 pwt = Tt[lj * TT + li];
-                const float cr = pw.x - pwt.x, ci = pw.y + pwt.y;
-                const float dr = (t1[q] - t2[q]) + cr;                       // dW = (PW @ Phalf) + comm   (:499,509)
-                const float di = ((t3[q] - t1[q]) - t2[q]) + ci;
-                dW_new[e] = make_float2(dr, di);
-                const float2 w = ep_W[e];
-                ep.Whalf[e] = make_float2(w.x + dr, w.y + di);               // Whalf = W + dW             (:481-482)
-                if (ep.fused) {
-                    // should this be the step's last iteration: W_next = W + 2 comm (:547,592), next Whalf = W_next + dW
-                    const float wr = w.x + 2.0f * cr, wi = w.y + 2.0f * ci;
-                    ep_Wnext[e] = make_float2(wr, wi);
-                    ep.Whalf_step[e] = make_float2(wr + dr, wi + di);
-                }
-                const float2 o = dW_old[e];
-                const float er = o.x - dr, ei = o.y - di;                    // |dW_old - dW|              (:526,534)
-                a = sqrtf(er * er + ei * ei);
-            }
-            // sum over the 32 lanes that share this row (fixed butterfly: deterministic), in double
-            double rsum = (double)a;
-            rsum = qf_row16_sum(rsum);      // (xor butterfly 1, 2, 4, 8 on DPP: same tree, same bits as four __shfl_xor steps)
-            rsum += __shfl_xor(rsum, 16, 64);
-            if (l31 == 0) rs[wn * CBM + li] = rsum;
-        }
-        __syncthreads();
-        if (tid < CBM && (EXACT || i0 + tid < N)) {
-            const double v = rs[tid] + rs[CBM + tid];
-            if (ep.fused) __hip_atomic_store(ep.rowpart + (size_t)tn * N + i0 + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else ep.rowpart[(size_t)tn * N + i0 + tid] = v;
-        }
-        if (ep.fused) {
-            // the last tile to get here closes the iteration (ticket: guide section 6 G16, counter form)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            unsigned *last_flag = reinterpret_cast<unsigned *>(rs + 2 * CBM);
-            if (tid == 0) {
-                const unsigned old = __hip_atomic_fetch_add(ep.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *last_flag = (old == (unsigned)(ep.n_tiles - 1)) ? 1u : 0u;
-            }
-            __syncthreads();
-            if (*last_flag != 0u)
-                qf_fused_step_end<1>(N, tiles_n, ep.rowpart, ep.ticket, ep.state_rw, ep.rec, guard.iter, tid, rs + 2 * CBM + 2);
-        }
-    }
-}
-
-// The plain product with the K range of a tile cut into KS parts INSIDE the workgroup: KS groups of four wavefronts, each
-// with its own LDS buffers and its own quarter (half) of the K-tiles, partial tiles added in group order at the end.
-// Why: at N = 1024 a launch is one 64 x 64 tile per CU, i.e. one wavefront per SIMD, and the fp32 matrix pipe idles
-// while that wavefront waits for its LDS reads and barriers -- the same kernel reaches 0.81 of the peak at N = 2048,
-// where four workgroups share a CU, against 0.59 at N = 1024.  More wavefronts per SIMD on the SAME tile give the
-// scheduler that choice without a second tile.  (N % (16 KS) == 0: every group runs the same number of barriers.)
-template <int KS>
-__global__ __launch_bounds__(256 * KS) void k_cgemm_ks(int N, int tiles_n, const float2 *__restrict__ A, const float2 *__restrict__ B,
-                                                        float2 *__restrict__ C, qf_guard guard)
-{
-    if (!qf_guard_iter(guard)) return;
-    if (guard.alt && guard.state->wh_sel) B = static_cast<const float2 *>(guard.alt);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    const int grp = threadIdx.x >> 8, tid = threadIdx.x & 255;
-    unsigned char *smem = smem_all + grp * CG_MAIN_BYTES;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tm = lid / tiles_n, tn = lid % tiles_n;
-    const int i0 = tm * CBM, j0 = tn * CBN;
-    const int a_row = tid >> 3, a_kp = tid & 7;
-    const int b_k = tid >> 5, b_jp = tid & 31;
-    float4 ra[2][2], rb[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) ra[x][y] = rb[x][y] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int KTp = (N / CBK) / KS, kb = grp * KTp;
-
-    auto load_tile = [&](int kt, float4 (&a)[2], float4 (&b)[2]) __attribute__((always_inline)) {
+    auto load_tile = [&](int kt, float4 (&a)[R], float4 (&b)[R]) __attribute__((always_inline)) {
         const int k0 = (kb + kt) * CBK;
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            a[r] = *reinterpret_cast<const float4 *>(A + (size_t)(i0 + a_row + 32 * r) * N + k0 + 2 * a_kp);
-            b[r] = *reinterpret_cast<const float4 *>(B + (size_t)(k0 + b_k + 8 * r) * N + j0 + 2 * b_jp);
+        for (int r = 0; r < R; ++r) {
+            a[r] = ld4_guarded<EXACT>(A, N, i0 + a_row + 32 * r, k0, 2 * a_kp);
+            b[r] = ld4_guarded<EXACT>(B, N, k0 + b_k + (256 / JP) * r, j0, 2 * b_jp);
         }
     };
-    auto store_tile = [&](int buf, const float4 (&a)[2], const float4 (&b)[2]) __attribute__((always_inline)) {
-        float2 *As = reinterpret_cast<float2 *>(smem + buf * A_BYTES);
-        float2 *Bs = reinterpret_cast<float2 *>(smem + 2 * A_BYTES + buf * B_BYTES);
+    auto store_tile = [&](int buf, const float4 (&a)[R], const float4 (&b)[R]) __attribute__((always_inline)) {
+        float2 *As = reinterpret_cast<float2 *>(smem + buf * T::A_BYTES);
+        float2 *Bs = reinterpret_cast<float2 *>(smem + 2 * T::A_BYTES + buf * T::B_BYTES);
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            As[(2 * a_kp) * SA + a_row + 32 * r] = make_float2(a[r].x, a[r].y);
-            As[(2 * a_kp + 1) * SA + a_row + 32 * r] = make_float2(a[r].z, a[r].w);
-            *reinterpret_cast<float4 *>(Bs + (b_k + 8 * r) * SB + 2 * b_jp) = b[r];
+        for (int r = 0; r < R; ++r) {
+            As[T::a_at(a_row + 32 * r, 2 * a_kp)] = make_float2(a[r].x, a[r].y);
+            As[T::a_at(a_row + 32 * r, 2 * a_kp + 1)] = make_float2(a[r].z, a[r].w);
+            *reinterpret_cast<float4 *>(Bs + (b_k + (256 / JP) * r) * T::BN + 2 * b_jp) = b[r];
         }
     };
-    v16f t1, t2, t3;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { t1[q] = 0.f; t2[q] = 0.f; t3[q] = 0.f; }
     auto compute = [&](int buf) __attribute__((always_inline)) {
-        const float2 *As = reinterpret_cast<const float2 *>(smem + buf * A_BYTES) + wm * 32 + l31;
-        const float2 *Bs = reinterpret_cast<const float2 *>(smem + 2 * A_BYTES + buf * B_BYTES) + wn * 32 + l31;
+        const float2 *As = reinterpret_cast<const float2 *>(smem + buf * T::A_BYTES) + T::a_at(wm * T::MF + lm, lk);
+        const float2 *Bs = reinterpret_cast<const float2 *>(smem + 2 * T::A_BYTES + buf * T::B_BYTES) + lk * T::BN + wn * T::MF + lm;
 #pragma unroll
-        for (int s = 0; s < CBK / 2; ++s) {
-            const float2 a = As[(2 * s + lh) * SA];
-            const float2 b = Bs[(2 * s + lh) * SB];
-            t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, t1, 0, 0, 0);
-            t2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, t2, 0, 0, 0);
-            t3 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x + a.y, b.x + b.y, t3, 0, 0, 0);
+        for (int s = 0; s < CBK / T::KM; ++s) {
+            const float2 a = As[T::a_at(0, T::KM * s)];
+            const float2 b = Bs[T::KM * s * T::BN];
+            t1 = T::mfma(a.x, b.x, t1);
+            t2 = T::mfma(a.y, b.y, t2);
+            t3 = T::mfma(a.x + a.y, b.x + b.y, t3);
         }
     };
+
     load_tile(0, ra[0], rb[0]);
     if (KTp > 1) load_tile(1, ra[1], rb[1]);
     store_tile(0, ra[0], rb[0]);
     __syncthreads();
     if (KTp > 2) load_tile(2, ra[0], rb[0]);
     int kt = 0;
+    // two K-tiles per trip: LDS buffer and register-set indices are literals.  (Staging K-tile kt+1 and issuing
+    // the loads of kt+3 AHEAD of K-tile kt's MFMAs instead of behind them measured slower: 81.9 against 78.5 us
+    // at N=1024, 456 against 437 at N=2048 -- the waves then meet the LDS store path all at once.)
     for (; kt + 1 < KTp; kt += 2) {
         compute(0);
-        store_tile(1, ra[1], rb[1]);
+        store_tile(1, ra[1], rb[1]);                       // K-tile kt+1 (arrived two K-tiles ago)
         if (kt + 3 < KTp) load_tile(kt + 3, ra[1], rb[1]);
         __syncthreads();
         compute(1);
@@ -335,27 +185,158 @@ __global__ __launch_bounds__(256 * KS) void k_cgemm_ks(int N, int tiles_n, const
         __syncthreads();
     }
     if (kt < KTp) compute(0);
-    // the groups' partial tiles through LDS ([group - 1][q][thread]: conflict-free), added in group order
-    __syncthreads();
-    float2 *X = reinterpret_cast<float2 *>(smem_all);
-    if (grp > 0) {
+    return {t1, t2, t3};
+}
+
+// ---- the second product's epilogue (32 x 32 tiles), shared by the full and the upper-triangle kernel.
+// The mirrored PW tile (rows j0.., columns i0..) goes through LDS (Tt[BN][TT]) so that both global reads of PW are
+// row-coalesced; conj_subtract_ (isospectral.py:71-74) needs PW[i,j] - conj(PW[j,i]).
+template <bool EXACT>
+__device__ __forceinline__ void cg_stage_pw_mirror(const float2 *__restrict__ PW, int N, int i0, int j0, int tid, float2 *Tt)
+{
+    typedef cg_small T;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) X[((grp - 1) * 16 + q) * 256 + tid] = make_float2(t1[q] - t2[q], (t3[q] - t1[q]) - t2[q]);
+    for (int r = 0; r < 2; ++r) {
+        const int row = (tid >> 4) + 16 * r, cp = tid & 15;
+        const float4 v = ld4_guarded<EXACT>(PW, N, j0 + row, i0, 2 * cp);
+        Tt[row * T::TT + 2 * cp] = make_float2(v.x, v.y);
+        Tt[row * T::TT + 2 * cp + 1] = make_float2(v.z, v.w);
     }
-    __syncthreads();
-    if (grp > 0) return;
+}
+
+// One entry: pw = PW[i,j], pwt = PW[j,i], (re, im) = (PW @ Phalf)[i,j], w = W[i,j], o = dW_old[i,j].  Returns |dW_old - dW|.
+__device__ __forceinline__ float cg_epilogue_entry(float2 pw, float2 pwt, float re, float im, float2 w, float2 o, float2 &dv, float2 &whv,
+                                                   float2 &wnv, float2 &whs)
+{
+    const float cr = pw.x - pwt.x, ci = pw.y + pwt.y;
+    const float dr = re + cr, di = im + ci;                      // dW = (PW @ Phalf) + comm   (:499,509)
+    dv = make_float2(dr, di);
+    whv = make_float2(w.x + dr, w.y + di);                       // Whalf = W + dW             (:481-482)
+    // should this be the step's last iteration: W_next = W + 2 comm (:547,592), next Whalf = W_next + dW
+    const float wr = w.x + 2.0f * cr, wi = w.y + 2.0f * ci;
+    wnv = make_float2(wr, wi);
+    whs = make_float2(wr + dr, wi + di);
+    const float er = o.x - dr, ei = o.y - di;                    // |dW_old - dW|              (:526,534)
+    return sqrtf(er * er + ei * ei);
+}
+
+// C = A @ B (EPI = false) or the second product with its fused epilogue (EPI = true):
+//   dW_new = A @ B + (PW - PW^H);  Whalf = W + dW_new;  rowpart[tile column][i] = sum_j |dW_old - dW_new|
+// KS > 1, the plain product with the K range of a tile cut into KS parts INSIDE the workgroup: KS groups of four
+// wavefronts, each with its own LDS buffers and its own 1/KS of the K-tiles, partial tiles added in group order at the end.
+// Why: at N = 1024 a launch is one 64 x 64 tile per CU, i.e. one wavefront per SIMD, and the fp32 matrix pipe idles
+// while that wavefront waits for its LDS reads and barriers -- the same kernel reaches 0.81 of the peak at N = 2048,
+// where four workgroups share a CU, against 0.59 at N = 1024.  More wavefronts per SIMD on the SAME tile give the
+// scheduler that choice without a second tile.  (N % (16 KS) == 0: every group runs the same number of barriers.)
+// Instantiated (qf_launch_cgemm): <32, false, true, 1 / 2 / 4>, <32, false, false, 1>, <32, true, true / false, 1>,
+// <64, false, true, 1 / 2 / 4>.  The second product lives on 32 x 32 tiles only: its 64 x 64 form lost at every size.
+template <int TILE, bool EPI, bool EXACT, int KS>
+__global__ __launch_bounds__(256 * KS) void k_cgemm(int N, int tiles_n, const float2 *__restrict__ A, const float2 *__restrict__ B,
+                                                    float2 *__restrict__ C, qf_epilogue_f ep, qf_guard guard)
+{
+    typedef cg_tile<TILE> T;
+    static_assert(!EPI || TILE == QF_C64_TILE, "the second product lives on 32 x 32 tiles");
+    static_assert(KS == 1 || (!EPI && EXACT), "K groups: plain product on an exact tiling");
+    static_assert(TILE == 32 || EXACT, "64 x 64 tiles: exact tilings only");
+    static_assert((KS - 1) * T::Q * 256 * (int)sizeof(float2) <= KS * T::MAIN_BYTES, "the groups' partial tiles fit the K loop's LDS");
+    if (!qf_guard_iter(guard)) return;
+    // fused step end: the first product of a step's first iteration takes the Whalf prepared for it
+    if (!EPI && guard.alt && guard.state->wh_sel) B = static_cast<const float2 *>(guard.alt);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+    const int grp = KS > 1 ? (int)(threadIdx.x >> 8) : 0;
+    unsigned char *const smem = KS > 1 ? smem_all + grp * T::MAIN_BYTES : smem_all;
+    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int lm = lane % T::MF, lk = lane / T::MF;
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tm = lid / tiles_n, tn = lid % tiles_n;
+    const int i0 = tm * T::BM, j0 = tn * T::BN;
+
+    const int KT = ((N + CBK - 1) / CBK) / KS;             // this group's K-tiles: grp KT .. grp KT + KT - 1
+    const cg_acc3<TILE> acc = cg_k_loop<TILE, EXACT>(A, B, N, i0, j0, grp * KT, KT, smem);
+    const typename T::acc t1 = acc.t1, t2 = acc.t2, t3 = acc.t3;
+
+    if constexpr (!EPI) {
+        // the groups' partial tiles through LDS ([group - 1][q][thread]: conflict-free), added in group order
+        float2 *X = reinterpret_cast<float2 *>(smem_all);
+        if constexpr (KS > 1) {
+            __syncthreads();
+            if (grp > 0) {
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        float re = t1[q] - t2[q], im = (t3[q] - t1[q]) - t2[q];
-#pragma unroll
-        for (int g = 1; g < KS; ++g) {
-            const float2 v = X[((g - 1) * 16 + q) * 256 + tid];
-            re += v.x;
-            im += v.y;
+                for (int q = 0; q < T::Q; ++q) X[((grp - 1) * T::Q + q) * 256 + tid] = make_float2(t1[q] - t2[q], (t3[q] - t1[q]) - t2[q]);
+            }
+            __syncthreads();
+            if (grp > 0) return;
         }
-        const int gi = i0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
-        const int gj = j0 + wn * 32 + l31;
-        C[(size_t)gi * N + gj] = make_float2(re, im);
+#pragma unroll
+        for (int q = 0; q < T::Q; ++q) {
+            const int gi = i0 + wm * T::MF + (q & 3) + 8 * (q >> 2) + 4 * lk;
+            const int gj = j0 + wn * T::MF + lm;
+            float re = t1[q] - t2[q], im = (t3[q] - t1[q]) - t2[q];
+            if constexpr (KS > 1) {
+#pragma unroll
+                for (int g = 1; g < KS; ++g) {
+                    const float2 v = X[((g - 1) * T::Q + q) * 256 + tid];
+                    re += v.x;
+                    im += v.y;
+                }
+            }
+            if (EXACT || (gi < N && gj < N)) C[(size_t)gi * N + gj] = make_float2(re, im);
+        }
+    } else {
+        const int parity = guard.state ? guard.state->dw_parity : 0;
+        const float2 *__restrict__ dW_old = ep.dW[parity];
+        float2 *__restrict__ dW_new = ep.dW[parity ^ 1];
+        // fused step end: the state is Wpair[w_parity]; the candidate next state goes to the other buffer
+        const int wpar = (ep.fused && guard.state) ? guard.state->w_parity : 0;
+        const float2 *__restrict__ ep_W = ep.fused ? ep.Wpair[wpar] : ep.W;
+        float2 *__restrict__ ep_Wnext = ep.fused ? ep.Wpair[wpar ^ 1] : nullptr;
+        __syncthreads();      // every wave is done with the K-loop buffers
+        float2 *Tt = reinterpret_cast<float2 *>(smem);
+        double *rs = reinterpret_cast<double *>(smem + T::TT_BYTES);   // [2][BM]
+        cg_stage_pw_mirror<EXACT>(ep.PW, N, i0, j0, tid, Tt);
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < T::Q; ++q) {
+            const int li = wm * T::MF + 4 * lk + q;
+            const int lj = wn * T::MF + lm;
+            const int gi = i0 + li, gj = j0 + lj;
+            float a = 0.f;
+            if (EXACT || (gi < N && gj < N)) {
+                const size_t e = (size_t)gi * N + gj;
+                float2 dv, whv, wnv, whs;
+                a = cg_epilogue_entry(ep.PW[e], Tt[lj * T::TT + li], t1[q] - t2[q], (t3[q] - t1[q]) - t2[q], ep_W[e], dW_old[e], dv, whv, wnv, whs);
+                dW_new[e] = dv;
+                ep.Whalf[e] = whv;
+                if (ep.fused) {
+                    ep_Wnext[e] = wnv;
+                    ep.Whalf_step[e] = whs;
+                }
+            }
+            // sum over the 16 lanes that share this row (fixed butterfly: deterministic), in double
+            double rsum = (double)a;
+            rsum = qf_row16_sum(rsum);      // (xor butterfly 1, 2, 4, 8 on DPP: same tree, same bits as four __shfl_xor steps)
+            if (lm == 0) rs[wn * T::BM + li] = rsum;
+        }
+        __syncthreads();
+        if (tid < T::BM && (EXACT || i0 + tid < N)) {
+            const double v = rs[tid] + rs[T::BM + tid];
+            if (ep.fused) __hip_atomic_store(ep.rowpart + (size_t)tn * N + i0 + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else ep.rowpart[(size_t)tn * N + i0 + tid] = v;
+        }
+        if (ep.fused) {
+            // the last tile to get here closes the iteration (ticket: guide section 6 G16, counter form)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            unsigned *last_flag = reinterpret_cast<unsigned *>(rs + 2 * T::BM);
+            if (tid == 0) {
+                const unsigned old = __hip_atomic_fetch_add(ep.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *last_flag = (old == (unsigned)(ep.n_tiles - 1)) ? 1u : 0u;
+            }
+            __syncthreads();
+            if (*last_flag != 0u)
+                qf_fused_step_end<1>(N, tiles_n, ep.rowpart, ep.ticket, ep.state_rw, ep.rec, guard.iter, tid, rs + 2 * T::BM + 2);
+        }
     }
 }
 
@@ -367,16 +348,16 @@ __global__ __launch_bounds__(256 * KS) void k_cgemm_ks(int N, int tiles_n, const
 // parks its partial tile (write-through), drains, takes a ticket on the tile's arrival counter and leaves unless it
 // came last; the last arrival adds ALL pieces from memory in piece order (its own included: the same bits whoever is
 // last) and runs the epilogue.  Nobody waits; the counters are monotone (`split` arrivals per executed launch).
-// 67 KiB of LDS: two workgroups share a CU, which is what lets 272 workgroups run on 256 CUs at once.
 // Below the diagonal only Whalf is written (the next first product's right operand): W and dW are read back on and
 // above the diagonal tiles only and restored once at the end of a call (k_mirror_lower<float2>, elementwise.hip).
-// On 32 x 32 tiles (any N >= 64; edge tiles guarded): k_cgemm32's K loop (one 16 x 16 MFMA tile per wavefront).  Partial tiles
-// are 8 KiB, the epilogue's LDS 17 KiB: many workgroups share a CU.  (A 64 x 64-tile form of this kernel existed in
-// rounds 3-4: slower at every size -- N = 1024 71.6 against 59.2 us, N = 2048 320 against 299 -- removed in round 5.)
+// On 32 x 32 tiles (any N >= 64; edge tiles guarded): one 16 x 16 MFMA tile per wavefront.  Partial tiles are 8 KiB, the
+// epilogue's LDS 18 KiB: many workgroups share a CU.  (A 64 x 64-tile form of this kernel existed in rounds 3-4: slower
+// at every size -- N = 1024 71.6 against 59.2 us, N = 2048 320 against 299 -- removed in round 5.)
 typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
-constexpr int ST_TILE_BYTES = SBM * STT * (int)sizeof(float2);
+constexpr int SBM = cg_small::BM, SBN = cg_small::BN, STT = cg_small::TT;
+constexpr int ST_TILE_BYTES = cg_small::TT_BYTES;
 constexpr int ST_EPI_BYTES = 2 * ST_TILE_BYTES + (4 * SBM + 16) * (int)sizeof(double);
-constexpr int ST_SMEM = SG_MAIN_BYTES > ST_EPI_BYTES ? SG_MAIN_BYTES : ST_EPI_BYTES;
+constexpr int ST_SMEM = cg_small::MAIN_BYTES > ST_EPI_BYTES ? cg_small::MAIN_BYTES : ST_EPI_BYTES;
 
 // EXACT = false: N is no multiple of 32 -- nt = ceil(N / 32) tile rows, loads, stores and row sums of the edge tiles guarded
 // (out-of-range operands are zeros: they add nothing to the products), K-tiles = ceil(N / 16).
@@ -421,70 +402,12 @@ __global__ __launch_bounds__(256) void k_cgemm_tri32(int N, int nt, const float2
     const float2 *__restrict__ ep_W = ep.fused ? ep.Wpair[wpar] : ep.W;
     float2 *__restrict__ ep_Wnext = ep.fused ? ep.Wpair[wpar ^ 1] : nullptr;
 
-    const int a_row = tid >> 3, a_kp = tid & 7;
-    const int b_k = tid >> 4, b_jp = tid & 15;
-    float4 ra[2], rb[2];
-    ra[0] = ra[1] = rb[0] = rb[1] = make_float4(0.f, 0.f, 0.f, 0.f);
     // this piece's K-tiles: kb .. kb + KTp - 1 (N % 32 == 0 makes the K-tile count even, not a multiple of 4: the pieces
     // of a tile may differ by one K-tile)
     const int KTN = (N + CBK - 1) / CBK;
     const int kb = (int)((long long)KTN * h / S), KTp = (int)((long long)KTN * (h + 1) / S) - kb;
-
-    auto load_tile = [&](int kt, float4 &a, float4 &b) __attribute__((always_inline)) {
-        const int k0 = (kb + kt) * CBK;
-        if (EXACT) {
-            a = *reinterpret_cast<const float4 *>(A + (size_t)(i0 + a_row) * N + k0 + 2 * a_kp);
-            b = *reinterpret_cast<const float4 *>(B + (size_t)(k0 + b_k) * N + j0 + 2 * b_jp);
-        } else {
-            const int gi = i0 + a_row, gk = k0 + 2 * a_kp;
-            a = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gi < N && gk + 1 < N) a = ld4<false>(A + (size_t)gi * N + gk);
-            else if (gi < N && gk < N) { const float2 t = A[(size_t)gi * N + gk]; a = make_float4(t.x, t.y, 0.f, 0.f); }
-            const int gkb = k0 + b_k, gj = j0 + 2 * b_jp;
-            b = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gkb < N && gj + 1 < N) b = ld4<false>(B + (size_t)gkb * N + gj);
-            else if (gkb < N && gj < N) { const float2 t = B[(size_t)gkb * N + gj]; b = make_float4(t.x, t.y, 0.f, 0.f); }
-        }
-    };
-    auto store_tile = [&](int buf, const float4 &a, const float4 &b) __attribute__((always_inline)) {
-        float2 *As = reinterpret_cast<float2 *>(smem + buf * SA_BYTES);
-        float2 *Bs = reinterpret_cast<float2 *>(smem + 2 * SA_BYTES + buf * SB_BYTES);
-        As[a_row * SAK + 2 * a_kp] = make_float2(a.x, a.y);
-        As[a_row * SAK + 2 * a_kp + 1] = make_float2(a.z, a.w);
-        *reinterpret_cast<float4 *>(Bs + b_k * SBN + 2 * b_jp) = b;
-    };
-    v4f t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f}, t3 = {0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-        const float2 *As = reinterpret_cast<const float2 *>(smem + buf * SA_BYTES) + (wm * 16 + l15) * SAK + lq;
-        const float2 *Bs = reinterpret_cast<const float2 *>(smem + 2 * SA_BYTES + buf * SB_BYTES) + lq * SBN + wn * 16 + l15;
-#pragma unroll
-        for (int s = 0; s < CBK / 4; ++s) {
-            const float2 a = As[4 * s];
-            const float2 b = Bs[4 * s * SBN];
-            t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, t1, 0, 0, 0);
-            t2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, t2, 0, 0, 0);
-            t3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x + a.y, b.x + b.y, t3, 0, 0, 0);
-        }
-    };
-    load_tile(0, ra[0], rb[0]);
-    if (KTp > 1) load_tile(1, ra[1], rb[1]);
-    store_tile(0, ra[0], rb[0]);
-    __syncthreads();
-    if (KTp > 2) load_tile(2, ra[0], rb[0]);
-    int kt = 0;
-    for (; kt + 1 < KTp; kt += 2) {
-        compute(0);
-        store_tile(1, ra[1], rb[1]);
-        if (kt + 3 < KTp) load_tile(kt + 3, ra[1], rb[1]);
-        __syncthreads();
-        compute(1);
-        if (kt + 2 < KTp) {
-            store_tile(0, ra[0], rb[0]);
-            if (kt + 4 < KTp) load_tile(kt + 4, ra[0], rb[0]);
-        }
-        __syncthreads();
-    }
-    if (kt < KTp) compute(0);
+    const cg_acc3<QF_C64_TILE> acc = cg_k_loop<QF_C64_TILE, EXACT>(A, B, N, i0, j0, kb, KTp, smem);
+    const v4f t1 = acc.t1, t2 = acc.t2, t3 = acc.t3;
 
     float re[4], im[4];
 #pragma unroll
@@ -533,16 +456,7 @@ __global__ __launch_bounds__(256) void k_cgemm_tri32(int N, int nt, const float2
     float2 *Th = reinterpret_cast<float2 *>(smem + ST_TILE_BYTES);
     double *rs = reinterpret_cast<double *>(smem + 2 * ST_TILE_BYTES);   // [2][32] row sums
     double *cs = rs + 2 * SBM;                                           // [2][32] column sums
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int row = (tid >> 4) + 16 * r, cp = tid & 15;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int gj = j0 + row, gi = i0 + 2 * cp;
-        if (EXACT || (gj < N && gi + 1 < N)) v = ld4<EXACT>(ep.PW + (size_t)gj * N + gi);
-        else if (gj < N && gi < N) { const float2 t = ep.PW[(size_t)gj * N + gi]; v = make_float4(t.x, t.y, 0.f, 0.f); }
-        Tt[row * STT + 2 * cp] = make_float2(v.x, v.y);
-        Tt[row * STT + 2 * cp + 1] = make_float2(v.z, v.w);
-    }
+    cg_stage_pw_mirror<EXACT>(ep.PW, N, i0, j0, tid, Tt);
     __syncthreads();
     float2 dv[4], whv[4], wnv[4], whs[4];
     double csum = 0.0;
@@ -554,22 +468,7 @@ __global__ __launch_bounds__(256) void k_cgemm_tri32(int N, int nt, const float2
         const bool in = EXACT || (i0 + li < N && j0 + lj < N);
         double a = 0.0;
         dv[q] = whv[q] = wnv[q] = whs[q] = make_float2(0.f, 0.f);
-        if (in) {
-            const float2 pw = ep.PW[e];
-            const float2 pwt = Tt[lj * STT + li];
-            const float cr = pw.x - pwt.x, ci = pw.y + pwt.y;
-            const float dr = re[q] + cr;
-            const float di = im[q] + ci;
-            dv[q] = make_float2(dr, di);
-            const float2 w = ep_W[e];
-            whv[q] = make_float2(w.x + dr, w.y + di);
-            const float wr = w.x + 2.0f * cr, wi = w.y + 2.0f * ci;
-            wnv[q] = make_float2(wr, wi);
-            whs[q] = make_float2(wr + dr, wi + di);
-            const float2 o = dW_old[e];
-            const float er = o.x - dr, ei = o.y - di;
-            a = (double)sqrtf(er * er + ei * ei);
-        }
+        if (in) a = (double)cg_epilogue_entry(ep.PW[e], Tt[lj * STT + li], re[q], im[q], ep_W[e], dW_old[e], dv[q], whv[q], wnv[q], whs[q]);
         csum += a;
         double rsum = a;
         rsum = qf_row16_sum(rsum);      // (xor butterfly 1, 2, 4, 8 on DPP: same tree, same bits as four __shfl_xor steps)
@@ -637,188 +536,9 @@ __global__ __launch_bounds__(256) void k_cgemm_tri32(int N, int nt, const float2
     }
 }
 
-// The same product on 32 x 32 block tiles (N < 768): 4 wavefronts (2 x 2), one 16 x 16 tile each.
-// MFMA f32 16x16x4 lane maps: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
-// C/D[row = 4 (lane >> 4) + reg][col = lane & 15].
-// KS > 1 (plain product, exact tilings): KS groups of four wavefronts on the same tile, each with its own LDS buffers and
-// its own 1/KS of the K-tiles (see k_cgemm_ks).
-template <bool EPI, bool EXACT, int KS = 1>
-__global__ __launch_bounds__(256 * KS) void k_cgemm32(int N, int tiles_n, const float2 *__restrict__ A, const float2 *__restrict__ B,
-                                                      float2 *__restrict__ C, qf_epilogue_f ep, qf_guard guard)
-{
-    if (!qf_guard_iter(guard)) return;
-    if (!EPI && guard.alt && guard.state->wh_sel) B = static_cast<const float2 *>(guard.alt);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    const int grp = KS > 1 ? (int)(threadIdx.x >> 8) : 0;
-    unsigned char *const smem = KS > 1 ? smem_all + grp * SG_MAIN_BYTES : smem_all;
-    const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tm = lid / tiles_n, tn = lid % tiles_n;
-    const int i0 = tm * SBM, j0 = tn * SBN;
-    const int parity = (EPI && guard.state) ? guard.state->dw_parity : 0;
-    const float2 *__restrict__ dW_old = ep.dW[parity];
-    float2 *__restrict__ dW_new = ep.dW[parity ^ 1];
-    // fused step end: the state is Wpair[w_parity]; the candidate next state goes to the other buffer
-    const int wpar = (EPI && ep.fused && guard.state) ? guard.state->w_parity : 0;
-    const float2 *__restrict__ ep_W = (EPI && ep.fused) ? ep.Wpair[wpar] : ep.W;
-    float2 *__restrict__ ep_Wnext = (EPI && ep.fused) ? ep.Wpair[wpar ^ 1] : nullptr;
-
-    // staging maps: A row tid / 8, k-pair tid % 8;  B k-row tid / 16, column pair tid % 16
-    const int a_row = tid >> 3, a_kp = tid & 7;
-    const int b_k = tid >> 4, b_jp = tid & 15;
-    float4 ra[2], rb[2];
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-
-    const int KT = ((N + CBK - 1) / CBK) / KS, kb = grp * KT;      // this group's K-tiles
-    auto load_tile = [&](int kt, float4 &a, float4 &b) {
-        const int k0 = (kb + kt) * CBK;
-        const int gi = i0 + a_row, gk = k0 + 2 * a_kp;
-        a = zero4;
-        if (EXACT || (gi < N && gk + 1 < N)) a = ld4<EXACT>(A + (size_t)gi * N + gk);
-        else if (gi < N && gk < N) { const float2 t = A[(size_t)gi * N + gk]; a = make_float4(t.x, t.y, 0.f, 0.f); }
-        const int gkb = k0 + b_k, gj = j0 + 2 * b_jp;
-        b = zero4;
-        if (EXACT || (gkb < N && gj + 1 < N)) b = ld4<EXACT>(B + (size_t)gkb * N + gj);
-        else if (gkb < N && gj < N) { const float2 t = B[(size_t)gkb * N + gj]; b = make_float4(t.x, t.y, 0.f, 0.f); }
-    };
-    auto store_tile = [&](int buf, const float4 &a, const float4 &b) {
-        float2 *As = reinterpret_cast<float2 *>(smem + buf * SA_BYTES);
-        float2 *Bs = reinterpret_cast<float2 *>(smem + 2 * SA_BYTES + buf * SB_BYTES);
-        As[a_row * SAK + 2 * a_kp] = make_float2(a.x, a.y);
-        As[a_row * SAK + 2 * a_kp + 1] = make_float2(a.z, a.w);
-        *reinterpret_cast<float4 *>(Bs + b_k * SBN + 2 * b_jp) = b;
-    };
-
-    v4f t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f}, t3 = {0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](int buf) {
-        const float2 *As = reinterpret_cast<const float2 *>(smem + buf * SA_BYTES) + (wm * 16 + l15) * SAK + lq;
-        const float2 *Bs = reinterpret_cast<const float2 *>(smem + 2 * SA_BYTES + buf * SB_BYTES) + lq * SBN + wn * 16 + l15;
-#pragma unroll
-        for (int s = 0; s < CBK / 4; ++s) {
-            const float2 a = As[4 * s];
-            const float2 b = Bs[4 * s * SBN];
-            t1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, t1, 0, 0, 0);
-            t2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, t2, 0, 0, 0);
-            t3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x + a.y, b.x + b.y, t3, 0, 0, 0);
-        }
-    };
-
-    load_tile(0, ra[0], rb[0]);
-    if (KT > 1) load_tile(1, ra[1], rb[1]);
-    store_tile(0, ra[0], rb[0]);
-    __syncthreads();
-    if (KT > 2) load_tile(2, ra[0], rb[0]);
-    int kt = 0;
-    for (; kt + 1 < KT; kt += 2) {
-        compute(0);
-        store_tile(1, ra[1], rb[1]);
-        if (kt + 3 < KT) load_tile(kt + 3, ra[1], rb[1]);
-        __syncthreads();
-        compute(1);
-        if (kt + 2 < KT) {
-            store_tile(0, ra[0], rb[0]);
-            if (kt + 4 < KT) load_tile(kt + 4, ra[0], rb[0]);
-        }
-        __syncthreads();
-    }
-    if (kt < KT) compute(0);
-
-    if constexpr (!EPI) {
-        float2 *X = reinterpret_cast<float2 *>(smem_all);       // KS > 1: [group - 1][q][thread]
-        if constexpr (KS > 1) {
-            __syncthreads();
-            if (grp > 0) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) X[((grp - 1) * 4 + q) * 256 + tid] = make_float2(t1[q] - t2[q], (t3[q] - t1[q]) - t2[q]);
-            }
-            __syncthreads();
-            if (grp > 0) return;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int gi = i0 + wm * 16 + 4 * lq + q;
-            const int gj = j0 + wn * 16 + l15;
-            float re = t1[q] - t2[q], im = (t3[q] - t1[q]) - t2[q];
-            if constexpr (KS > 1) {
-#pragma unroll
-                for (int g = 1; g < KS; ++g) {
-                    const float2 v = X[((g - 1) * 4 + q) * 256 + tid];
-                    re += v.x;
-                    im += v.y;
-                }
-            }
-            if (EXACT || (gi < N && gj < N)) C[(size_t)gi * N + gj] = make_float2(re, im);
-        }
-    } else {
-        __syncthreads();
-        float2 *Tt = reinterpret_cast<float2 *>(smem);
-        double *rs = reinterpret_cast<double *>(smem + SBM * STT * sizeof(float2));   // [2][SBM]
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int row = (tid >> 4) + 16 * r, cp = tid & 15;
-            const int gj = j0 + row, gi = i0 + 2 * cp;
-            float4 v = zero4;
-            if (EXACT || (gj < N && gi + 1 < N)) v = ld4<EXACT>(ep.PW + (size_t)gj * N + gi);
-            else if (gj < N && gi < N) { const float2 t = ep.PW[(size_t)gj * N + gi]; v = make_float4(t.x, t.y, 0.f, 0.f); }
-            Tt[row * STT + 2 * cp] = make_float2(v.x, v.y);
-            Tt[row * STT + 2 * cp + 1] = make_float2(v.z, v.w);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int li = wm * 16 + 4 * lq + q;
-            const int lj = wn * 16 + l15;
-            const int gi = i0 + li, gj = j0 + lj;
-            float a = 0.f;
-            if (EXACT || (gi < N && gj < N)) {
-                const size_t e = (size_t)gi * N + gj;
-                const float2 pw = ep.PW[e];
-                const float2 pwt = Tt[lj * STT + li];
-                const float cr = pw.x - pwt.x, ci = pw.y + pwt.y;
-                const float dr = (t1[q] - t2[q]) + cr;
-                const float di = ((t3[q] - t1[q]) - t2[q]) + ci;
-                dW_new[e] = make_float2(dr, di);
-                const float2 w = ep_W[e];
-                ep.Whalf[e] = make_float2(w.x + dr, w.y + di);
-                if (ep.fused) {
-                    const float wr = w.x + 2.0f * cr, wi = w.y + 2.0f * ci;
-                    ep_Wnext[e] = make_float2(wr, wi);
-                    ep.Whalf_step[e] = make_float2(wr + dr, wi + di);
-                }
-                const float2 o = dW_old[e];
-                const float er = o.x - dr, ei = o.y - di;
-                a = sqrtf(er * er + ei * ei);
-            }
-            double rsum = (double)a;
-            rsum = qf_row16_sum(rsum);      // (xor butterfly 1, 2, 4, 8 on DPP: same tree, same bits as four __shfl_xor steps)
-            if (l15 == 0) rs[wn * SBM + li] = rsum;
-        }
-        __syncthreads();
-        if (tid < SBM && (EXACT || i0 + tid < N)) {
-            const double v = rs[tid] + rs[SBM + tid];
-            if (ep.fused) __hip_atomic_store(ep.rowpart + (size_t)tn * N + i0 + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else ep.rowpart[(size_t)tn * N + i0 + tid] = v;
-        }
-        if (ep.fused) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            unsigned *last_flag = reinterpret_cast<unsigned *>(rs + 2 * SBM);
-            if (tid == 0) {
-                const unsigned old = __hip_atomic_fetch_add(ep.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *last_flag = (old == (unsigned)(ep.n_tiles - 1)) ? 1u : 0u;
-            }
-            __syncthreads();
-            if (*last_flag != 0u)
-                qf_fused_step_end<1>(N, tiles_n, ep.rowpart, ep.ticket, ep.state_rw, ep.rec, guard.iter, tid, rs + 2 * SBM + 2);
-        }
-    }
-}
-
 }  // namespace
 
-// Tile sizes of the complex64 products.  The 32 x 32 kernels are small (18-34 KiB of LDS, 50-82 registers): several
+// Tile sizes of the complex64 products.  The 32 x 32 kernels are small (17-18 KiB of LDS, about 60 registers): several
 // workgroups share a CU, so they neither leave CUs idle when the tile count is no multiple of 256 nor need N % 64 == 0.
 // Measured (bench.py --dtype c64, timesteps/s, all products on 64 x 64 / on 32 x 32 tiles): N = 768 9,698 / 12,315; 832
 // 9,275 / 11,092; 896 8,856 / 9,232; 960 8,391 / 8,434; 1024 7,216 / 7,757; 1056 3,016 / 6,475 (64 x 64: generic path);
@@ -827,26 +547,20 @@ __global__ __launch_bounds__(256 * KS) void k_cgemm32(int N, int tiles_n, const 
 // against 71.6 us, N = 2048 299 against 320); the plain FIRST product is faster on 64 x 64 tiles where those fill the
 // chip (us, 64 / 32: N = 896 52.3 / 54.2, 960 56.1 / 58.2, 1024 59.0 / 61.8, 2048 402 / 433) and slower elsewhere (768
 // 46.1 / 38.5, 1088 113 / 78, 1280 132 / 124, 1536 230 / 188, 1792 348 / 305).
-// Rules: second product 32 x 32 at every N;
+// (No exact tiling: guarded 32 x 32 kernels -- N = 1000 3,586 -> 5,922 timesteps/s against the generic 64 x 64 path, N = 900
+// 3,907 -> 6,406, N = 1500 1,666 -> 2,180.)
+// Rules: second product 32 x 32 at every N (QF_C64_TILE);
 // first product 64 x 64 for N % 64 == 0 with 896 <= N <= 1024 or, from N = 2048 on, tiles filling >= 85 % of their rounds.
-int qf_c64_tile(const qf_ctx *ctx)
-{
-    (void)ctx;
-    // (no exact tiling: the generic paths with bounds checks either way -- N = 1000 3,586 -> 5,922 timesteps/s on the 32 x 32
-    // kernels, N = 900 3,907 -> 6,406, N = 1500 1,666 -> 2,180)
-    return SBM;
-}
-
 int qf_c64_tile_first(const qf_ctx *ctx)
 {
     const int N = ctx->N;
-    if (N % CBM != 0) return SBM;
-    if (N >= 896 && N <= 1024) return CBM;
+    if (N % 64 != 0) return 32;
+    if (N >= 896 && N <= 1024) return 64;
     if (N >= 2048) {
-        const long long tiles = (long long)(N / CBM) * (N / CBM), rounds = (tiles + 255) / 256;
-        return tiles * 100 >= rounds * 256 * 85 ? CBM : SBM;
+        const long long tiles = (long long)(N / 64) * (N / 64), rounds = (tiles + 255) / 256;
+        return tiles * 100 >= rounds * 256 * 85 ? 64 : 32;
     }
-    return SBM;
+    return 32;
 }
 
 int qf_c64_alloc(qf_ctx *ctx)
@@ -868,7 +582,7 @@ int qf_c64_alloc(qf_ctx *ctx)
         qf_c64_free(f);
         return QF_ERR_HIP;
     }
-    f->rowpart_tiles = qf_c64_tile(ctx) == SBM ? (N + SBN - 1) / SBN : (N + CBN - 1) / CBN;     // column tiles of the second product in use
+    f->rowpart_tiles = (N + QF_C64_TILE - 1) / QF_C64_TILE;     // column tiles of the second product
     if (hipMalloc((void **)&f->rowpart, (size_t)f->rowpart_tiles * N * sizeof(double)) != hipSuccess) {
         qf_set_error("qf_c64_alloc: out of device memory (N=%d)", N);
         qf_c64_free(f);
@@ -903,96 +617,68 @@ static void note_c64(qf_ctx *ctx, const char *kernel, int tile, int tiles, int g
                  kernel, mfma, tile, tile, tiles, (double)tiles / (double)grid_tiles, wgs, threads, step_end);
 }
 
+// one square product: KS groups of 256 threads per tile, each with the K loop's LDS (a request above 64 KiB needs the
+// dynamic-LDS limit of the kernel raised first: qf_smem_attr_set does that, once per instantiation and device)
+template <int TILE, bool EPI, bool EXACT, int KS>
+static int launch_cgemm(qf_ctx *ctx, int tiles_n, const float2 *A, const float2 *B, float2 *C, const qf_epilogue_f &ep, qf_guard guard)
+{
+    constexpr int smem = KS * cg_tile<TILE>::MAIN_BYTES;
+    static qf_smem_attr attr;
+    QF_TRY(qf_smem_attr_set(attr, (const void *)k_cgemm<TILE, EPI, EXACT, KS>, ctx->device, smem));
+    hipLaunchKernelGGL((k_cgemm<TILE, EPI, EXACT, KS>), dim3(tiles_n * tiles_n), dim3(256 * KS), smem, ctx->stream, ctx->N, tiles_n, A, B, C, ep,
+                       guard);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+template <int TILE>
+static int launch_cgemm_plain(qf_ctx *ctx, int ks, int tiles_n, const float2 *A, const float2 *B, float2 *C, qf_guard guard)
+{
+    const qf_epilogue_f none;
+    return ks == 4   ? launch_cgemm<TILE, false, true, 4>(ctx, tiles_n, A, B, C, none, guard)
+           : ks == 2 ? launch_cgemm<TILE, false, true, 2>(ctx, tiles_n, A, B, C, none, guard)
+                     : launch_cgemm<TILE, false, true, 1>(ctx, tiles_n, A, B, C, none, guard);
+}
+
 int qf_launch_cgemm(qf_ctx *ctx, const float2 *A, const float2 *B, float2 *C, const qf_epilogue_f *ep_in, qf_guard guard)
 {
     const int N = ctx->N;
-    qf_epilogue_f ep_copy;
-    const qf_epilogue_f *ep = ep_in;
-    if (ep_in && ep_in->fused) {     // tile ticket + what the last tile's workgroup updates
-        ep_copy = *ep_in;
-        const int t = qf_c64_tile(ctx) == SBM ? (N + SBM - 1) / SBM : (N + CBM - 1) / CBM;
-        ep_copy.ticket = ctx->ticket + 403;
-        ep_copy.n_tiles = t * t;
-        ep_copy.state_rw = ctx->state;
-        ep_copy.rec = ctx->host_rec;
-        ep = &ep_copy;
-    }
-    if ((ep ? qf_c64_tile(ctx) : qf_c64_tile_first(ctx)) == SBM) {
-        const int tm = (N + SBM - 1) / SBM, tn = (N + SBN - 1) / SBN;
-        const bool ex = (N % SBM == 0) && (N % CBK == 0);
-        qf_epilogue_f none_s;
-        dim3 grid_s(tm * tn), block_s(256);
-        if (!ep && ex) {
-            // one tile per CU or fewer: more wavefronts per SIMD on the same tile
-            const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-            int ks = tm * tn <= cus ? 4 : tm * tn <= 2 * cus ? 2 : 1;
-            while (ks > 1 && (N / CBK) % (2 * ks) != 0) ks >>= 1;
-            if (ks == 4 || ks == 2) note_c64(ctx, ks == 4 ? "k_cgemm32<plain, 4 K groups>" : "k_cgemm32<plain, 2 K groups>", SBM, tm * tn, tm * tn, tm * tn, 256 * ks, "v_mfma_f32_16x16x4_f32", "none");
-            if (ks == 4) {
-                static qf_smem_attr attr4;
-                QF_TRY(qf_smem_attr_set(attr4, (const void *)k_cgemm32<false, true, 4>, ctx->device, 4 * SG_MAIN_BYTES));
-                hipLaunchKernelGGL((k_cgemm32<false, true, 4>), grid_s, dim3(1024), 4 * SG_MAIN_BYTES, ctx->stream, N, tn, A, B, C, none_s, guard);
-                QF_HIP(hipGetLastError());
-                return QF_OK;
-            }
-            if (ks == 2) {
-                hipLaunchKernelGGL((k_cgemm32<false, true, 2>), grid_s, dim3(512), 2 * SG_MAIN_BYTES, ctx->stream, N, tn, A, B, C, none_s, guard);
-                QF_HIP(hipGetLastError());
-                return QF_OK;
-            }
-        }
-        note_c64(ctx, ep ? "k_cgemm32<EPI>" : "k_cgemm32<plain>", SBM, tm * tn, tm * tn, tm * tn, 256, "v_mfma_f32_16x16x4_f32",
-                 !ep ? "none" : ep->fused ? "fused (last tile decides)" : "two-kernel");
-        if (ep) {
-            if (ex) hipLaunchKernelGGL((k_cgemm32<true, true>), grid_s, block_s, SG_SMEM, ctx->stream, N, tn, A, B, C, *ep, guard);
-            else hipLaunchKernelGGL((k_cgemm32<true, false>), grid_s, block_s, SG_SMEM, ctx->stream, N, tn, A, B, C, *ep, guard);
-        } else {
-            if (ex) hipLaunchKernelGGL((k_cgemm32<false, true>), grid_s, block_s, SG_SMEM, ctx->stream, N, tn, A, B, C, none_s, guard);
-            else hipLaunchKernelGGL((k_cgemm32<false, false>), grid_s, block_s, SG_SMEM, ctx->stream, N, tn, A, B, C, none_s, guard);
-        }
-        QF_HIP(hipGetLastError());
-        return QF_OK;
-    }
-    const int tiles_m = (N + CBM - 1) / CBM, tiles_n = (N + CBN - 1) / CBN;
-    const bool exact = (N % CBM == 0) && (N % CBK == 0);
-    if (!ep && exact) {
-        // few tiles per CU: more wavefronts per SIMD on the same tile (k_cgemm_ks)
+    const int tile = ep_in ? QF_C64_TILE : qf_c64_tile_first(ctx);      // (64 x 64: only for N % 64 == 0)
+    const int nt = (N + tile - 1) / tile, tiles = nt * nt;
+    const bool exact = N % tile == 0;
+    // plain product on an exact tiling with two tiles per CU or fewer: K groups, more wavefronts per SIMD on the same tile
+    // (every group takes an even number of K-tiles)
+    int ks = 1;
+    if (!ep_in && exact) {
         const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-        int ks = tiles_m * tiles_n <= cus ? 4 : tiles_m * tiles_n <= 2 * cus ? 2 : 1;
+        ks = tiles <= cus ? 4 : tiles <= 2 * cus ? 2 : 1;
         while (ks > 1 && (N / CBK) % (2 * ks) != 0) ks >>= 1;
-        if (ks > 1) {
-            static qf_smem_attr attr2, attr4;
-            note_c64(ctx, ks == 4 ? "k_cgemm_ks<4>" : "k_cgemm_ks<2>", CBM, tiles_m * tiles_n, tiles_m * tiles_n, tiles_m * tiles_n, 256 * ks, "v_mfma_f32_32x32x2_f32", "none");
-            if (ks == 2) {
-                QF_TRY(qf_smem_attr_set(attr2, (const void *)k_cgemm_ks<2>, ctx->device, 2 * CG_MAIN_BYTES));
-                hipLaunchKernelGGL(k_cgemm_ks<2>, dim3(tiles_m * tiles_n), dim3(512), 2 * CG_MAIN_BYTES, ctx->stream, N, tiles_n, A, B, C, guard);
-            } else {
-                QF_TRY(qf_smem_attr_set(attr4, (const void *)k_cgemm_ks<4>, ctx->device, 4 * CG_MAIN_BYTES));
-                hipLaunchKernelGGL(k_cgemm_ks<4>, dim3(tiles_m * tiles_n), dim3(1024), 4 * CG_MAIN_BYTES, ctx->stream, N, tiles_n, A, B, C, guard);
-            }
-            QF_HIP(hipGetLastError());
-            return QF_OK;
+    }
+    const char *name = tile == 32 ? (ks == 4   ? "k_cgemm32<plain, 4 K groups>"
+                                     : ks == 2 ? "k_cgemm32<plain, 2 K groups>"
+                                     : ep_in   ? "k_cgemm32<EPI>"
+                                               : "k_cgemm32<plain>")
+                                  : (ks == 4 ? "k_cgemm_ks<4>" : ks == 2 ? "k_cgemm_ks<2>" : "k_cgemm<plain>");
+    note_c64(ctx, name, tile, tiles, tiles, tiles, 256 * ks, tile == 32 ? "v_mfma_f32_16x16x4_f32" : "v_mfma_f32_32x32x2_f32",
+             !ep_in ? "none" : ep_in->fused ? "fused (last tile decides)" : "two-kernel");
+    if (ep_in) {
+        qf_epilogue_f ep = *ep_in;
+        if (ep.fused) {     // tile ticket + what the last tile's workgroup updates
+            ep.ticket = ctx->ticket + 403;
+            ep.n_tiles = tiles;
+            ep.state_rw = ctx->state;
+            ep.rec = ctx->host_rec;
         }
+        return exact ? launch_cgemm<QF_C64_TILE, true, true, 1>(ctx, nt, A, B, C, ep, guard)
+                     : launch_cgemm<QF_C64_TILE, true, false, 1>(ctx, nt, A, B, C, ep, guard);
     }
-    qf_epilogue_f none;
-    dim3 grid(tiles_m * tiles_n), block(256);
-    note_c64(ctx, ep ? "k_cgemm<EPI>" : "k_cgemm<plain>", CBM, tiles_m * tiles_n, tiles_m * tiles_n, tiles_m * tiles_n, 256, "v_mfma_f32_32x32x2_f32",
-             !ep ? "none" : ep->fused ? "fused (last tile decides)" : "two-kernel");
-    if (ep) {
-        if (exact) hipLaunchKernelGGL((k_cgemm<true, true>), grid, block, CG_SMEM, ctx->stream, N, tiles_n, A, B, C, *ep, guard);
-        else hipLaunchKernelGGL((k_cgemm<true, false>), grid, block, CG_SMEM, ctx->stream, N, tiles_n, A, B, C, *ep, guard);
-    } else {
-        if (exact) hipLaunchKernelGGL((k_cgemm<false, true>), grid, block, CG_SMEM, ctx->stream, N, tiles_n, A, B, C, none, guard);
-        else hipLaunchKernelGGL((k_cgemm<false, false>), grid, block, CG_SMEM, ctx->stream, N, tiles_n, A, B, C, none, guard);
-    }
-    QF_HIP(hipGetLastError());
-    return QF_OK;
+    if (!exact) return launch_cgemm<32, false, false, 1>(ctx, nt, A, B, C, qf_epilogue_f(), guard);
+    return tile == 32 ? launch_cgemm_plain<32>(ctx, ks, nt, A, B, C, guard) : launch_cgemm_plain<64>(ctx, ks, nt, A, B, C, guard);
 }
 
 int qf_c64_tri_alloc(qf_ctx *ctx)
 {
     qf_c64 *f = ctx->c64;
-    const int tb = SBM;          // the upper-triangle product lives on 32 x 32 tiles (qf_c64_tile)
+    const int tb = QF_C64_TILE;
     if (!f || ctx->N < 64) {
         qf_set_error("qf_c64_tri_alloc: the upper-triangle product needs N >= 64 (N=%d)", ctx->N);
         return QF_ERR_INVALID;
@@ -1000,7 +686,7 @@ int qf_c64_tri_alloc(qf_ctx *ctx)
     if (f->tri_arrive) return QF_OK;
     const int nt = (ctx->N + tb - 1) / tb;
     const size_t tiles = (size_t)nt * (nt + 1) / 2;
-    // K pieces per off-diagonal / diagonal tile.  A workgroup is small (18 KiB of LDS, 82 registers), several share a CU
+    // K pieces per off-diagonal / diagonal tile.  A workgroup is small (18 KiB of LDS, 62 registers), several share a CU
     // and the pieces of a tile spread over them.  Measured (timesteps/s; full product / pieces 1,1 / 2,2 / 4,4 / 4,2):
     // N = 512 20,175 / 21,603 / 22,982 / 23,663 / 23,753; N = 704 12,498 / 14,331 / 15,224 / 15,415 / 14,759; N = 256
     // 30,769 / 32,017 / 32,632 / 33,249 / 33,335.

@@ -415,6 +415,14 @@ def test_kernel_resources(built):
         "k_solve<float, 8, 1, 0>": 4,
         "k_decide": 6,
     }
+    # the complex64 products (single.hip): exactly the instantiations the launchers use -- nine square kernels, two triangle
+    # kernels; every 32 x 32 one shares a SIMD eight ways (at most 64 registers), the 64 x 64 plain products four ways (at most 128)
+    c64 = {"k_cgemm<32, false, true, %d>" % ks: 8 for ks in (1, 2, 4)}
+    c64.update({"k_cgemm<32, false, false, 1>": 8, "k_cgemm<32, true, true, 1>": 8, "k_cgemm<32, true, false, 1>": 8,
+                "k_cgemm_tri32<true>": 8, "k_cgemm_tri32<false>": 8})
+    c64.update({"k_cgemm<64, false, true, %d>" % ks: 4 for ks in (1, 2, 4)})
+    assert sorted(k for k, v in res.items() if v["unit"] == "single.res") == sorted(c64), sorted(k for k, v in res.items() if v["unit"] == "single.res")
+    floors.update(c64)
     for name, floor in floors.items():
         assert name in res, (name, sorted(k for k in res if k.startswith(name.split("<")[0]))[:12])
         assert res[name]["occupancy"] >= floor, (name, res[name])

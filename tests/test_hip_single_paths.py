@@ -153,11 +153,8 @@ def test_float_solve_fold_switch(qfa, oracle, monkeypatch, N, fold):
 FIRST_TILE = {832: 32, 896: 64, 960: 64, 992: 32, 1088: 32, 2048: 64, 2112: 64, 2176: 64, 2304: 32, 3072: 64, 4096: 64}
 
 
-@pytest.mark.parametrize("N", sorted(FIRST_TILE))
-def test_cgemm_at_the_tile_rule(qfa, oracle, N):
-    """qf_cgemm on both sides of qf_c64_tile_first (64 x 64 tiles for N % 64 == 0 with 896 <= N <= 1024, and from 2048 on
-    where the tiles fill >= 85 % of their rounds of 256: 2112 just above, 2304 below), with the operand structure and the
-    bound of test_cgemm_vs_numpy; the tile the stepper's first product used at that N, from its plan."""
+def _cgemm_within_bound(N):
+    """qf_cgemm at N with the operand structure and the bound of test_cgemm_vs_numpy."""
     from quflow_amd import _lib
     from quflow_amd.context import Context, ptr
     rng = np.random.default_rng(N)
@@ -175,8 +172,44 @@ def test_cgemm_at_the_tile_rule(qfa, oracle, N):
     bound = 4 * EPS32 * (np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64)).max() * np.sqrt(N)
     assert maxabs(C, ref) <= bound, maxabs(C, ref) / bound
     assert np.all(C[:, 0] == 0)
+
+
+@pytest.mark.parametrize("N", sorted(FIRST_TILE))
+def test_cgemm_at_the_tile_rule(qfa, oracle, N):
+    """qf_cgemm on both sides of qf_c64_tile_first (64 x 64 tiles for N % 64 == 0 with 896 <= N <= 1024, and from 2048 on
+    where the tiles fill >= 85 % of their rounds of 256: 2112 just above, 2304 below), with the operand structure and the
+    bound of test_cgemm_vs_numpy; the tile the stepper's first product used at that N, from its plan."""
+    _cgemm_within_bound(N)
     plan = stepper_plan(qfa, make_W0_c64(oracle, N, 1))
     assert plan["first_product"]["tile"][0] == FIRST_TILE[N], (N, plan["first_product"])
+
+
+# N: (kernel, tile, threads) of the plain first product on 256 CUs.  K groups (qf_launch_cgemm): exact tilings only; four
+# groups of 256 threads up to one tile per CU, two up to two tiles per CU, halved until every group gets an even number of
+# K-tiles of 16 ((N / 16) % (2 groups) == 0).
+K_GROUP_RULE = {
+    64: ("k_cgemm32<plain, 2 K groups>", 32, 512),       # 4 K-tiles: 4 groups impossible, 2 fit
+    96: ("k_cgemm32<plain>", 32, 256),                   # 6 K-tiles divide by neither 8 nor 4
+    100: ("k_cgemm32<plain>", 32, 256),                  # guarded tiling: never grouped
+    128: ("k_cgemm32<plain, 4 K groups>", 32, 1024),     # smallest 4-group case
+    544: ("k_cgemm32<plain>", 32, 256),                  # 289 tiles -> 2 groups wanted, 34 K-tiles refuse
+    576: ("k_cgemm32<plain, 2 K groups>", 32, 512),      # 324 tiles, between one and two per CU
+    736: ("k_cgemm32<plain>", 32, 256),                  # 529 tiles > 2 per CU
+    896: ("k_cgemm_ks<4>", 64, 1024),
+    960: ("k_cgemm_ks<2>", 64, 512),                     # 60 K-tiles: 8 does not divide
+    1024: ("k_cgemm_ks<4>", 64, 1024),
+    2048: ("k_cgemm<plain>", 64, 256),                   # four tiles per CU
+}
+
+
+@pytest.mark.parametrize("N", sorted(K_GROUP_RULE))
+def test_cgemm_k_group_rule(qfa, oracle, N):
+    """The K-group rule of the plain complex64 product, from the plan of a one-step run: which kernel, tile and workgroup
+    size the first product takes at sizes on both sides of every clause of the rule, and qf_cgemm at that size within the
+    bound of test_cgemm_vs_numpy (the grouped 32 x 32 variants at their smallest sizes)."""
+    plan = stepper_plan(qfa, make_W0_c64(oracle, N, 1))["first_product"]
+    assert (plan["kernel"], plan["tile"][0], plan["threads"]) == K_GROUP_RULE[N], (N, plan)
+    _cgemm_within_bound(N)
 
 
 # ============================================================================= B. stepper options against the oracle

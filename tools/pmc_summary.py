@@ -15,11 +15,12 @@ def short(name):
         return "k_zgemm_tri"
     if "k_cgemm_tri" in name:
         return "k_cgemm_tri"
-    if "k_cgemm_ks" in name:
-        return "k_cgemm_ks"
-    if "k_cgemm32" in name or "k_cgemm" in name:
-        flat = name.replace(" ", "")
-        return ("k_cgemm32" if "k_cgemm32" in name else "k_cgemm") + ("<EPI>" if "<true," in flat else "<plain>")
+    if "k_cgemm<" in name:
+        # k_cgemm<TILE, EPI, EXACT, KS>, under the labels of the plan: the 64 x 64 product with K groups is k_cgemm_ks
+        tile, epi, _, ks = name.replace(" ", "").split("k_cgemm<")[1].split(">")[0].split(",")
+        if tile == "64":
+            return "k_cgemm_ks" if ks != "1" else "k_cgemm<plain>"
+        return "k_cgemm32" + ("<EPI>" if epi == "true" else "<plain>")
     if "k_oz_gemm" in name:
         flat = name.replace(" ", "")
         digits = flat.split("k_oz_gemm<")[1].split(",")[0] if "k_oz_gemm<" in flat else "?"
