@@ -272,9 +272,16 @@ int qf_erk_states(qf_ctx *ctx, void *states_host, int k, int method, double dt, 
 /* ---- isomp_simple (isospectral.py:254-335) and isomp_quasinewton (isospectral.py:155-251) on the
  *      ctx state W, hamiltonian = solve_poisson, skew-Hermitian case.  The reference's two
  *      lu_solve calls per pass (A = I - (stepsize/2) Ptilde) are replaced by a Newton-Schulz
- *      inverse on the matrix cores (A is always well conditioned for skew-Hermitian Ptilde).
+ *      inverse on the matrix cores (cond(A) = sqrt(1 + |E|_2^2) for skew-Hermitian E = (stepsize/2) Ptilde).
  *      qf_isomp_quasinewton: tol < 0 -> 'auto' (eps*stepsize*|W|_inf, :190-191);
- *      stats: total_iterations, number_of_maxit (steps whose loop ran out), tol_used. ------ */
+ *      stats: total_iterations, number_of_maxit (steps whose loop ran out), tol_used.
+ *      Envelope of the inverse: states agree with the reference's LU to 1e-12 up to |E|_inf = 100 and to 8 times the
+ *      spread of two CPU evaluations at 1000 (tests/test_hip_lu_steppers.py).  Beyond: cond(A)^2 = (1 + s_max^2) /
+ *      (1 + s_min^2) of E's singular values, so for a stream function without a null vector the scale of E does not
+ *      matter up to the refusal; with one, cond(A) = |E|_2 and from |E|_2 ~ 1e8 on the residual's rounding noise stays
+ *      above the iteration's exit level: QF_ERR_STATE ("Newton-Schulz did not converge"; the reference's LU has lost
+ *      the state there too, eps cond(A)^2).  |E|_inf > 1e150 is refused at once, QF_ERR_STATE ("too large for the
+ *      Newton-Schulz inverse").  An error, never a wrong state. ------ */
 int qf_isomp_simple(qf_ctx *ctx, double dt, int steps);
 int qf_isomp_quasinewton(qf_ctx *ctx, double dt, int steps, double tol, int maxit, qf_isomp_stats *stats_out);
 /* ... with a foreign `hamiltonian(Wtilde)` (isospectral.py:207, 286): the `hamiltonian` / `user` members of a
@@ -557,6 +564,12 @@ int qf_debug_guard_check(long long *allocations, long long *damaged, char *first
  * must agree bit for bit in the normal range -- the iteration counts rest on it.  n <= N*N of the context. */
 int qf_debug_modulus(qf_ctx *ctx, int n, const double *er_host, const double *ei_host, double *out_modulus_host,
                      double *out_sqrt_host);
+/* What the Newton-Schulz inverse did in the last qf_isomp_simple / qf_isomp_quasinewton call (plain or hooked) of this
+ * context: out[0] inversions asked for, out[1] cold starts (no inverse yet, or the previous one's residual against the new
+ * A was not below 0.5), out[2] inverses kept as they were (A moved by no more than the inverse's rounding noise), out[3]
+ * Newton-Schulz iterations in all.  The general branch of isomp_simple inverts twice per step; both count.  Counted on the
+ * host, reset when such a call starts, read-only. */
+int qf_ns_stats(qf_ctx *ctx, long long out[4]);
 /* C = A @ B for host matrices through the MFMA zgemm of the stepper (parity tests of
  * the commutator pair, isospectral.py:496,499). */
 int qf_zgemm(qf_ctx *ctx, const void *A_host, const void *B_host, void *C_host);

@@ -175,6 +175,7 @@ SIGNATURES = {
     "qf_plan_describe": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
     "qf_device_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
     "qf_debug_modulus": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    "qf_ns_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong)]),
     "qf_profile_stride": (ctypes.c_int, [_vp, ctypes.c_int]),
     "qf_profile_seen": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
     "qf_timer_start": (ctypes.c_int, [_vp]),

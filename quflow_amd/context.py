@@ -46,6 +46,13 @@ class Context:
         self._lib.qf_plan_describe(self.handle, buf, n + 1)
         return json.loads(buf.value.decode())
 
+    def ns_stats(self):
+        """What the Newton-Schulz inverse did in the last isomp_simple / isomp_quasinewton call on this context
+        (qf_ns_stats): inversions, cold starts, inverses kept and iterations, both inverses of the general branch summed."""
+        out = (ctypes.c_longlong * 4)()
+        _lib.check(self._lib.qf_ns_stats(self.handle, out))
+        return dict(zip(("inversions", "cold_starts", "kept", "iterations"), (int(v) for v in out)))
+
     def close(self):
         if self.handle:
             self._lib.qf_ctx_destroy(self.handle)

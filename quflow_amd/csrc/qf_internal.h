@@ -415,6 +415,7 @@ struct qf_ctx {
     size_t hook_host_bytes = 0;
     cplx *ns_inv = nullptr;  // Newton-Schulz inverse of I - E (isomp_simple / isomp_quasinewton), on demand
     cplx *ns_tmp = nullptr;
+    long long ns_counts[4] = {0, 0, 0, 0};   // the last LU-stepper call's inversions, cold starts, inverses kept, iterations (qf_ns_stats)
 
     double *lap = nullptr;   // (N,N,2) coefficient table of the Poisson problem (bc=True)
     qf_factors poisson;      // its factorisation
