@@ -149,10 +149,15 @@ __global__ __launch_bounds__(1024) void k_oz_slice(int N, qf_oz_jobs jobs, qf_gu
         v[4] = p1.x; v[5] = p1.y; v[6] = p1.z; v[7] = p1.w;
     }
     double m = 0.0;
+    bool isnan_ = false;         // fmax drops a NaN: a row with one counts as a row with an inf (m = inf, below)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmax(m, fabs(v[j]));
+    for (int j = 0; j < 8; ++j) {
+        m = fmax(m, fabs(v[j]));
+        isnan_ |= v[j] != v[j];
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+    if (__builtin_amdgcn_ballot_w64(isnan_) != 0ull) m = __builtin_inf();
     if (pair && jj == 1) {       // the diagonal entry's imaginary part: lane partial, wave tree, waves in order
         double d = 0.0;
 #pragma unroll
@@ -180,7 +185,13 @@ __global__ __launch_bounds__(1024) void k_oz_slice(int N, qf_oz_jobs jobs, qf_gu
         const double f = frexp(m, &e);      // m = f 2^e, f in [0.5, 1)
         e += (f <= 0.984375) ? 1 : 2;       // y = x/s in [-63/128, 63/128]
     }
-    const double s = ldexp(1.0, e), inv_s = ldexp(1.0, -e);
+    // Two edge rules.  A row whose scale would be below the smallest normal power of two (a subnormal row maximum: 1 / s
+    // overflows, and the mantissa bits of the fma's inf / NaN would become the digits) is flushed: zero digits, s = 1 -- what
+    // is lost is below N 2^-1023 times the column's scale.  A row with an inf or a NaN in it gets the scale NaN, so its whole
+    // row (column, for the right operand) of the product is NaN instead of the finite number its mantissa bits would cut to.
+    const bool flush = e < -1022;
+    if (flush) e = 0;
+    const double s = (m == __builtin_inf()) ? __builtin_nan("") : ldexp(1.0, e), inv_s = flush ? 0.0 : ldexp(1.0, -e);
     if (tid == 0) jb.scale[row] = s;
     // Digits.  The offset bytes d_t + 64 of the balanced digits d_t in [-64, 63] are the plain base-128 digits of
     // z = y + B, B = sum_t 64 128^-(t+1) = 0.5039... (z in (0.011, 0.997)):

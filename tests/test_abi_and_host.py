@@ -414,6 +414,8 @@ def test_kernel_resources(built):
         "k_solve<double, 32, 1, 0>": 1,                      # above
         "k_solve<float, 8, 1, 0>": 4,
         "k_decide": 6,
+        "k_oz_slice<5>": 6,                                  # int8 products: one workgroup of up to 1024 lanes per row
+        "k_oz_slice<6>": 5,
     }
     # the complex64 products (single.hip): exactly the instantiations the launchers use -- nine square kernels, two triangle
     # kernels; every 32 x 32 one shares a SIMD eight ways (at most 64 registers), the 64 x 64 plain products four ways (at most 128)
