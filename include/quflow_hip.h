@@ -231,7 +231,13 @@ int qf_isomp(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit
  * reference spans many steps and zeroes dW once (isospectral.py:430), so a host that must act
  * between the steps -- strang_splitting (isospectral.py:466-467, 598-599) or callback (:549-550) --
  * issues the first step with qf_isomp and every further one with qf_isomp_continue (the state may
- * be re-uploaded in between: Whalf restarts as W + dW, isospectral.py:481-482). */
+ * be re-uploaded in between: Whalf restarts as W + dW, isospectral.py:481-482).
+ * What ends a carried increment (the next qf_isomp_continue then starts from dW = 0, as qf_isomp does): every other call
+ * that replaces the state or uses dW[] as scratch -- qf_erk / qf_erk_hooked, qf_isomp_simple / _quasinewton (plain and hooked),
+ * qf_isomp_hooked / qf_isomp_forced, qf_rotate(NULL), qf_shr2mat(NULL) / qf_shc2mat(NULL), qf_states_select --, a call that
+ * ended in an error, and for the complex64 state qf_c64_upload_W and qf_c64_solve_tridiagonal.  What keeps it: qf_upload_W
+ * and the resident form of qf_solve_tridiagonal (the two ways a Strang half step reaches the state) and every host-in /
+ * host-out or read-only entry point (tests/test_hip_context_carry.py runs each of them between the two calls). */
 int qf_isomp_continue(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit,
                       int compsum, int reinitialize, qf_isomp_stats *stats_out);
 

@@ -1,6 +1,7 @@
 """Device contexts: one `qf_ctx` per (device, N), created once and cached --
 the analogue of constructing IsompCUDA(N, dtype) / DiagTriDiagOp(N, dtype) once
 (quflow/experimental/isospectral_cuda.py:52-80, quflow/simulation.py:554-562)."""
+import contextlib
 import ctypes
 import os
 
@@ -65,9 +66,9 @@ class Context:
             pass
 
 
-def _cached(cache, N, device):
+def _cached(cache, N, device, *more):
     dev = default_device() if device is None else int(device)
-    key = (dev, int(N))
+    key = (dev, int(N)) + more
     ctx = cache.get(key)
     if ctx is None:
         try:
@@ -87,14 +88,40 @@ def get_context(N, device=None):
 
 
 _stepper_contexts = {}
+_nested_stepper_contexts = {}       # (device, N, depth >= 1): handed out while the contexts of the lower depths are in use
+_stepper_depth = {}                 # (device, N): hooked stepper calls in progress (stepper_context)
 
 
-def get_stepper_context(N, device=None):
+def get_stepper_context(N, device=None, depth=0):
     """A context of its own for a stepper call that runs user hooks while its trajectory is resident on
     the device: the hooks may call the host-in/host-out entry points (solve_poisson, energy_euler,
     solve_viscdamp, ...), which stage through the shared per-N context of get_context() and would
-    otherwise overwrite the resident state."""
-    return _cached(_stepper_contexts, N, device)
+    otherwise overwrite the resident state.  `depth` > 0: the further context of a hooked stepper call made
+    from inside a hook of another one (stepper_context)."""
+    if depth == 0:
+        return _cached(_stepper_contexts, N, device)
+    return _cached(_nested_stepper_contexts, N, device, int(depth))
+
+
+@contextlib.contextmanager
+def stepper_context(N, device=None, get=None):
+    """The stepper context of one hooked stepper call, held for the call: `with stepper_context(N) as ctx`.  A hook that
+    itself calls a hooked stepper at the same (device, N) -- `strang_splitting=lambda h, W: heun(W, h, 1, forcing=f)`, a
+    forecast inside a `callback` -- is handed a further context, so it cannot touch the state, the carried increment
+    or the scratch matrices of the trajectory it interrupts: nested calls are independent, as the reference's are.
+    Every context stays cached under its depth for the next call that nests as deep; the depth is given back on the
+    way out, after an exception too.  No lock: one context is used by one host thread at a time (quflow_hip.h).
+    `get`: the getter to call, get_stepper_context by default."""
+    key = (default_device() if device is None else int(device), int(N))
+    depth = _stepper_depth.get(key, 0)
+    _stepper_depth[key] = depth + 1
+    try:
+        yield (get or get_stepper_context)(N, device, depth)
+    finally:
+        if depth:
+            _stepper_depth[key] = depth
+        else:
+            _stepper_depth.pop(key, None)
 
 
 def release_idle_contexts():
@@ -102,7 +129,7 @@ def release_idle_contexts():
     theirs and keep them); returns how many were closed.  Called when a new context does not fit on the device."""
     import sys
     closed = 0
-    for cache in (_contexts, _stepper_contexts):
+    for cache in (_contexts, _stepper_contexts, _nested_stepper_contexts):
         for key in list(cache):
             ctx = cache[key]
             if sys.getrefcount(ctx) <= 3:       # the cache, `ctx`, getrefcount's own argument
@@ -114,10 +141,10 @@ def release_idle_contexts():
 
 
 def release_contexts():
-    for ctx in list(_contexts.values()) + list(_stepper_contexts.values()):
-        ctx.close()
-    _contexts.clear()
-    _stepper_contexts.clear()
+    for cache in (_contexts, _stepper_contexts, _nested_stepper_contexts):
+        for ctx in cache.values():
+            ctx.close()
+        cache.clear()
     _result_cache.clear()
 
 

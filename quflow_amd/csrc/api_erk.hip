@@ -35,13 +35,17 @@ struct erk_state { cplx *X, *Xp, *acc, *F, *P; };
 struct erk_source { std::function<int(bool from_state)> eval, late; };
 
 // host != nullptr: the states come from there and go back there.  probe: one product per stage (X@P = (P@X)^H) if every state
-// is exactly skew-Hermitian.  clears_skew: ctx->w_skew_known is cleared (every entry but qf_erk_states, which leaves ctx->W alone).
+// is exactly skew-Hermitian.  clears_skew: ctx->w_skew_known is cleared and a carried increment ended -- the state is replaced and
+// ctx->dW[0] is the stage accumulator -- (every entry but qf_erk_states, which leaves ctx->W and ctx->dW[] alone).
 int erk_body(qf_ctx *ctx, std::vector<erk_state> &S, void *host, bool probe, bool clears_skew, int method, double dt, int steps,
              const erk_source &src)
 {
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     const double inv_hb = 1.0 / qf_hbar(ctx->N);
-    if (clears_skew) ctx->w_skew_known = false;
+    if (clears_skew) {
+        ctx->w_skew_known = false;
+        ctx->increment_valid = false;
+    }
     bool one_product = probe;
     for (size_t j = 0; j < S.size(); ++j) {
         if (host) QF_HIP(hipMemcpyAsync(S[j].X, (const char *)host + j * mbytes, mbytes, hipMemcpyHostToDevice, ctx->stream));

@@ -959,19 +959,25 @@ int c64_fixedpoint_products(const char *name, bool tri, qf_ctx *ctx, const void 
     QF_HIP(hipMemcpyAsync(f->Phalf, Phalf_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     QF_HIP(hipMemcpyAsync(f->Whalf, Whalf_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     QF_HIP(hipMemcpyAsync(f->stage, W_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    QF_HIP(hipMemcpyAsync(f->dW[0], dW_old_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    // (dW_old, dW_new: the second buffers of the fused step end's pairs, not f->dW[] -- as qf_fixedpoint_products)
+    if (!f->W2) QF_HIP(hipMalloc((void **)&f->W2, bytes));
+    if (!f->Whalf2) QF_HIP(hipMalloc((void **)&f->Whalf2, bytes));
+    float2 *dW_old = f->W2, *dW_new = f->Whalf2;
+    QF_HIP(hipMemcpyAsync(dW_old, dW_old_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     QF_TRY(qf_launch_cgemm(ctx, f->Phalf, f->Whalf, f->PW, nullptr));
     qf_epilogue_f ep = epilogue_of(f, false);
     ep.W = f->stage;
-    // unguarded: parity 0, writes dW[1] (the triangle product: on and above the diagonal tiles)
+    ep.dW[0] = dW_old;
+    ep.dW[1] = dW_new;
+    // unguarded: parity 0, writes ep.dW[1] (the triangle product: on and above the diagonal tiles)
     if (tri) {
         QF_TRY(qf_launch_cgemm_tri(ctx, f->PW, f->Phalf, &ep));
-        QF_TRY(qf_launch_mirror_lower(ctx, f->dW[1]));
+        QF_TRY(qf_launch_mirror_lower(ctx, dW_new));
     } else {
         QF_TRY(qf_launch_cgemm(ctx, f->PW, f->Phalf, nullptr, &ep));
     }
     QF_TRY(qf_launch_sum_rowpart(ctx, f->rowpart, f->rowpart_tiles, ctx->rowsum));      // (both forms: column tiles of QF_C64_TILE)
-    QF_HIP(hipMemcpyAsync(dW_new_host, f->dW[1], bytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipMemcpyAsync(dW_new_host, dW_new, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipMemcpyAsync(Whalf_new_host, f->Whalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipMemcpyAsync(rowsum_host, ctx->rowsum, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
@@ -1064,10 +1070,17 @@ int qf_fixedpoint_products(qf_ctx *ctx, const void *Phalf_host, const void *Whal
     QF_HIP(hipMemcpyAsync(ctx->Phalf, Phalf_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     QF_HIP(hipMemcpyAsync(ctx->Whalf, Whalf_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     QF_HIP(hipMemcpyAsync(ctx->stage, W_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    QF_HIP(hipMemcpyAsync(ctx->dW[0], dW_old_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    // dW_old and dW_new take the second buffers of the fused step end's pairs, which are free between stepper calls, not
+    // ctx->dW[]: the increment a qf_isomp call left there for qf_isomp_continue stays as it is
+    if (!ctx->W2) QF_HIP(hipMalloc((void **)&ctx->W2, bytes));
+    if (!ctx->Whalf2) QF_HIP(hipMalloc((void **)&ctx->Whalf2, bytes));
+    cplx *dW_old = ctx->W2, *dW_new = ctx->Whalf2;
+    QF_HIP(hipMemcpyAsync(dW_old, dW_old_host, bytes, hipMemcpyHostToDevice, ctx->stream));
     QF_TRY(qf_launch_zgemm(ctx, ctx->Phalf, ctx->Whalf, ctx->PW, nullptr));
     qf_epilogue ep = epilogue_of(ctx, false);
     ep.W = ctx->stage;
+    ep.dW[0] = dW_old;
+    ep.dW[1] = dW_new;
     const bool saved = ctx->gemm_tri, saved32 = ctx->gemm_tri32;
     const int s_min = ctx->sk_min_units, s_epi = ctx->sk_epi_units, s_so = ctx->tri32_split, s_sd = ctx->tri32_split_diag;
     ctx->gemm_tri = (variant == 1);
@@ -1080,7 +1093,7 @@ int qf_fixedpoint_products(qf_ctx *ctx, const void *Phalf_host, const void *Whal
         if (so == 1 || so == 2 || so == 4) ctx->tri32_split = so;
         if (sd == 1 || sd == 2 || sd == 4) ctx->tri32_split_diag = sd;
     }
-    int rc = qf_launch_zgemm(ctx, ctx->PW, ctx->Phalf, nullptr, &ep);   // unguarded: parity 0, writes dW[1]
+    int rc = qf_launch_zgemm(ctx, ctx->PW, ctx->Phalf, nullptr, &ep);   // unguarded: parity 0, writes ep.dW[1]
     ctx->gemm_tri = saved;
     ctx->gemm_tri32 = saved32;
     ctx->sk_min_units = s_min;
@@ -1090,7 +1103,7 @@ int qf_fixedpoint_products(qf_ctx *ctx, const void *Phalf_host, const void *Whal
     QF_TRY(rc);
     // row sums of |dW_old - dW_new| in the fixed slot order k_norm_decide uses
     QF_TRY(qf_launch_sum_rowpart(ctx, ctx->rowpart, variant == 1 ? ctx->N / 64 : variant == 2 ? (ctx->N + 31) / 32 : ctx->rowpart_tiles, ctx->rowsum));
-    QF_HIP(hipMemcpyAsync(dW_new_host, ctx->dW[1], bytes, hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipMemcpyAsync(dW_new_host, dW_new, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipMemcpyAsync(Whalf_new_host, ctx->Whalf, bytes, hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipMemcpyAsync(rowsum_host, ctx->rowsum, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));

@@ -126,6 +126,8 @@ int qf_solve_tridiagonal(qf_ctx *ctx, const double *lap_host, unsigned long long
         // from pageable memory returns after staging, so the caller's buffer is free on return)
     }
     if (resident) {     // W <- T^-1 W (a Strang half step of a viscous / damped run between device steps)
+        // (a carried increment stays, as through qf_upload_W: the reference's dW lives through strang_splitting,
+        // isospectral.py:466-482; only `stage` is written besides W)
         if (!skewh) ctx->w_skew_known = false;   // (the skew-Hermitian solve mirrors exactly: the property survives)
         QF_HIP(hipMemcpyAsync(ctx->stage, ctx->W, NN * sizeof(cplx), hipMemcpyDeviceToDevice, ctx->stream));
         QF_TRY(qf_launch_solve(ctx, f, ctx->stage, ctx->W, 1.0, skewh));

@@ -197,6 +197,7 @@ static int isomp_simple_impl(qf_ctx *ctx, double dt, int steps, const qf_isomp_h
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     const double stepsize = dt / qf_hbar(ctx->N);           // isospectral.py:281
     ctx->w_skew_known = false;
+    ctx->increment_valid = false;    // (the state is replaced: no increment for qf_isomp_continue to carry)
     ns_work w;
     QF_TRY(ns_setup(ctx, w));
     const bool general_branch = hooks && !hooks->skewh;      // select_skewherm(False): isospectral.py:303-314
@@ -266,6 +267,7 @@ static int isomp_quasinewton_impl(qf_ctx *ctx, double dt, int steps, double tol,
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     const double stepsize = dt / qf_hbar(ctx->N);           // isospectral.py:187
     ctx->w_skew_known = false;
+    ctx->increment_valid = false;    // (dW[0], dW[1] are Wtilde_new and the residual below)
     if (tol < 0) {                                          // isospectral.py:190-191
         double nrm = 0.0;
         QF_TRY(qf_norm_inf_W(ctx, &nrm));

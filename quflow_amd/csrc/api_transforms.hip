@@ -146,7 +146,10 @@ int qf_shr2mat(qf_ctx *ctx, const double *omega_host, long long n_omega, void *W
         ctx->sh_shr_count = ncopy;
     }
     cplx *dst = W_host ? ctx->stage : ctx->W;
-    if (!W_host) ctx->w_skew_known = false;
+    if (!W_host) {       // the resident state is replaced: as after qf_rotate(NULL), no increment is carried
+        ctx->w_skew_known = false;
+        ctx->increment_valid = false;
+    }
     QF_TRY(qf_launch_shr2mat(ctx, Nmax, ctx->sh_omega, dst));
     if (W_host) QF_HIP(hipMemcpyAsync(W_host, dst, (size_t)NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
@@ -193,7 +196,10 @@ int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host)
     QF_HIP(hipMemcpyAsync(ctx->sh_omega, omega_host, NN * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
     ctx->sh_shr_count = 0;     // (complex now)
     cplx *dst = W_host ? ctx->stage : ctx->W;
-    if (!W_host) ctx->w_skew_known = false;
+    if (!W_host) {       // the resident state is replaced: as after qf_rotate(NULL), no increment is carried
+        ctx->w_skew_known = false;
+        ctx->increment_valid = false;
+    }
     QF_TRY(qf_launch_shc2mat(ctx, ctx->sh_omega, dst));
     if (W_host) QF_HIP(hipMemcpyAsync(W_host, dst, NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from . import laplacian as _laplacian
-from .context import Context, default_device, get_context, get_stepper_context, ptr
+from .context import Context, default_device, get_context, get_stepper_context, ptr, stepper_context
 from .geometry import hbar
 
 
@@ -108,6 +108,12 @@ def _installable(h, W):
         h.check_size(W.shape[-1])
         return h
     return None
+
+
+def _stepper_context(N, device):
+    """The stepper context of one hooked call, held for the call (context.stepper_context): a hooked stepper called from
+    inside one of this call's hooks gets a further context and leaves this call's trajectory alone."""
+    return stepper_context(N, device, get_stepper_context)
 
 
 @contextlib.contextmanager
@@ -335,28 +341,24 @@ def _device_tol(W, dt, tol, compsum):
 
 def _isomp_stepwise(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
                     reinitialize, device, ham=None):
-    if ham is None:
-        return _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
-                                  reinitialize, device)
     if not isinstance(W, np.ndarray) or W.ndim != 2 or W.shape[0] != W.shape[1]:
         raise ValueError("W must be a square matrix")
     _tol_arg(tol)
     # (an installed TridiagonalHamiltonian: the same loop, on the same stepper context, with it in force)
-    with _hamiltonian_on(get_stepper_context(W.shape[-1], device), ham):
+    with _stepper_context(W.shape[-1], device) as ctx, _hamiltonian_on(ctx, ham):
         return _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
-                                  reinitialize, device)
+                                  reinitialize, ctx)
 
 
 def _isomp_stepwise_on(W, dt, steps, strang_splitting, stats, callback, tol, maxit, minit, verbatim, compsum,
-                       reinitialize, device):
+                       reinitialize, ctx):
     """strang_splitting / callback around device steps (built-in Hamiltonian): one step per
     qf_isomp / qf_isomp_continue call, the tolerance fixed once from the initial state as in the
     reference (isospectral.py:440-452)."""
-    if not isinstance(W, np.ndarray) or W.ndim != 2 or W.shape[0] != W.shape[1]:
-        raise ValueError("W must be a square matrix")
     N = W.shape[-1]
     tol_c = _tol_arg(tol)
-    ctx = get_stepper_context(N, device)      # the hooks may use the shared context (solve_viscdamp, energy_euler, ...)
+    # (`ctx`: the call's stepper context -- the hooks may use the shared context (solve_viscdamp, energy_euler, ...) and
+    # call hooked steppers of their own)
     Wc = np.ascontiguousarray(W, dtype=np.complex128)
     if tol_c < 0:
         tol_c = float(_auto_tol(W, dt, compsum))
@@ -584,9 +586,9 @@ def _hooked_call(table, W, Wc, k, dt, steps, time, tol, tol_c, tol_report, minit
     table.c.has_time = int(time is not None)
     table.c.time = float(time) if time is not None else 0.0
     auto = isinstance(tol, str) or tol < 0
-    ctx = get_stepper_context(W.shape[-1], device)
     st = _lib.IsompStats()
-    with _hamiltonian_on(ctx, ham), _forcing_on(ctx, aff):       # (`native`: the device's own solve, of what is installed)
+    # (`native`: the device's own solve, of what is installed)
+    with _stepper_context(W.shape[-1], device) as ctx, _hamiltonian_on(ctx, ham), _forcing_on(ctx, aff):
         rc = ctx._lib.qf_isomp_hooked(ctx.handle, ptr(Wc), k, float(dt), int(steps), tol_c, int(minit),
                                       int(maxit), int(bool(compsum)), int(bool(reinitialize)), ctypes.byref(table.c),
                                       ctypes.byref(st))
@@ -756,17 +758,18 @@ def isomp_quasinewton(W, dt, steps=100, hamiltonian=_laplacian.solve_poisson, fo
         with _hamiltonian_on(ctx, ham):
             _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
             _lib.check(ctx._lib.qf_isomp_quasinewton(ctx.handle, float(dt), int(steps), tol_c, int(maxit), ctypes.byref(st)))
+        _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     else:
         # a foreign Hamiltonian (isospectral.py:207): called back once per pass on host copies; the linear solves and
         # the update stay on the device.  A context of its own: the hook may use the shared one.  With
         # select_skewherm(False) the reference runs the very same formulas (its `assert NotImplementedError(...)`,
         # :188-189, asserts a truthy object) on the general branch of the Poisson solve.
-        ctx = get_stepper_context(W.shape[-1], kwargs.get("device"))
-        table = _lu_hook_table(W.shape[-1], hamiltonian)
-        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-        table.check(ctx._lib.qf_isomp_quasinewton_hooked(ctx.handle, float(dt), int(steps), tol_c, int(maxit),
-                                                         ctypes.byref(st), ctypes.byref(table.c)))
-    _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
+        with _stepper_context(W.shape[-1], kwargs.get("device")) as ctx:
+            table = _lu_hook_table(W.shape[-1], hamiltonian)
+            _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+            table.check(ctx._lib.qf_isomp_quasinewton_hooked(ctx.handle, float(dt), int(steps), tol_c, int(maxit),
+                                                             ctypes.byref(st), ctypes.byref(table.c)))
+            _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     if Wc is not W:
         W[...] = Wc
     stats = kwargs.get("stats")
@@ -790,13 +793,14 @@ def isomp_simple(W, dt, steps=100, hamiltonian=_laplacian.solve_poisson, forcing
         with _hamiltonian_on(ctx, ham):
             _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
             _lib.check(ctx._lib.qf_isomp_simple(ctx.handle, float(dt), int(steps)))
+        _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     else:
         # a foreign Hamiltonian (isospectral.py:286) and / or select_skewherm(False): the general branch (:303-314)
-        ctx = get_stepper_context(W.shape[-1], kwargs.get("device"))
-        table = _lu_hook_table(W.shape[-1], hamiltonian)
-        _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
-        table.check(ctx._lib.qf_isomp_simple_hooked(ctx.handle, float(dt), int(steps), ctypes.byref(table.c)))
-    _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
+        with _stepper_context(W.shape[-1], kwargs.get("device")) as ctx:
+            table = _lu_hook_table(W.shape[-1], hamiltonian)
+            _lib.check(ctx._lib.qf_upload_W(ctx.handle, ptr(Wc)))
+            table.check(ctx._lib.qf_isomp_simple_hooked(ctx.handle, float(dt), int(steps), ctypes.byref(table.c)))
+            _lib.check(ctx._lib.qf_download_W(ctx.handle, ptr(Wc)))
     if Wc is not W:
         W[...] = Wc
     return W
@@ -844,8 +848,7 @@ def _erk(method, W, dt, steps, hamiltonian, forcing, device=None):
             table.set_forcing(forcing, False)
         if not _is_native_hamiltonian(hamiltonian):
             table.set_hamiltonian(hamiltonian, False, per_state=(None if k > 1 else False))
-        ctx = get_stepper_context(N, device)
-        with _forcing_on(ctx, aff):
+        with _stepper_context(N, device) as ctx, _forcing_on(ctx, aff):
             if stacked:
                 rc = ctx._lib.qf_erk_states_hooked(ctx.handle, ptr(Wc), int(k), *call, ctypes.byref(table.c))
             else:

@@ -362,6 +362,83 @@ def test_idle_contexts_make_room_when_a_new_one_does_not_fit(monkeypatch):
     assert context.get_context(128).N == 128 and 32 in closed    # 32 is idle now and makes room
 
 
+def test_nested_stepper_contexts_are_distinct_and_given_back(monkeypatch):
+    """quflow_amd/context.py, stepper_context: a hooked stepper call holds its stepper context for the call; a hooked stepper
+    called from one of its hooks at the same (device, N) gets a further one -- never the context whose trajectory it
+    interrupts --, which stays cached for the next call that nests as deep.  The depth is given back on the way out, after an
+    exception in the hook and after a failed creation too.  release_idle_contexts / release_contexts know the further ones.
+    Every hooked call site of integrators.py goes through it."""
+    from quflow_amd import context, integrators, _lib
+
+    made, closed = [0], []
+
+    class FakeContext:
+        fail = False
+
+        def __init__(self, N, device=None):
+            if FakeContext.fail:
+                raise _lib.QuflowHipError("QF_ERR_NO_DEVICE: qf_ctx_create: no HIP device")
+            self.N, self.device, self.handle = N, device, object()
+            made[0] += 1
+
+        def close(self):
+            if self.handle is not None:
+                self.handle = None
+                closed.append(self.N)
+
+    monkeypatch.setattr(context, "Context", FakeContext)
+    for name in ("_contexts", "_stepper_contexts", "_nested_stepper_contexts", "_stepper_depth"):
+        monkeypatch.setattr(context, name, {})
+    monkeypatch.setattr(context, "_default_device", 0)
+
+    with context.stepper_context(16) as a:
+        assert a is context.get_stepper_context(16)                 # the outermost call: the context tests and tools look at
+        with integrators._stepper_context(16, None) as b:           # (what the call sites of integrators.py use)
+            assert b is not a and b.N == 16
+            with context.stepper_context(16) as c:
+                assert c is not a and c is not b
+            with context.stepper_context(32) as d:                  # another size: a depth of its own
+                assert d is context.get_stepper_context(32)
+            with context.stepper_context(16, device=1) as e:        # another device too
+                assert e is context.get_stepper_context(16, 1) and e is not a
+        assert context._stepper_depth == {(0, 16): 1}
+        with context.stepper_context(16) as b2:
+            assert b2 is b                                          # the inner one went back to the cache
+    assert context._stepper_depth == {} and made[0] == 5
+    with context.stepper_context(16) as a2:
+        assert a2 is a
+
+    with pytest.raises(ZeroDivisionError):                          # an exception inside the inner hook releases both
+        with context.stepper_context(16) as x:
+            with context.stepper_context(16) as y:
+                assert (x, y) == (a, b)
+                1 / 0
+    assert context._stepper_depth == {}
+    FakeContext.fail = True                                         # a context that cannot be created takes no depth with it
+    with context.stepper_context(16):
+        with context.stepper_context(16):
+            with context.stepper_context(16):
+                with pytest.raises(_lib.QuflowHipError, match="no HIP device"):
+                    with context.stepper_context(16):
+                        pass
+            assert context._stepper_depth == {(0, 16): 2}
+    assert context._stepper_depth == {}
+    FakeContext.fail = False
+
+    del a, a2, b, b2, c, d, e, x, y
+    assert context.release_idle_contexts() == 5 and sorted(closed) == [16, 16, 16, 16, 32]
+    assert not context._stepper_contexts and not context._nested_stepper_contexts
+    with context.stepper_context(8):
+        with context.stepper_context(8):
+            pass
+    context.release_contexts()
+    assert sorted(closed)[:2] == [8, 8] and not context._stepper_contexts and not context._nested_stepper_contexts
+
+    # no hooked call site reaches for the one cached context any more
+    src = open(os.path.join(REPO, "quflow_amd", "integrators.py")).read()
+    assert len(re.findall(r"\bget_stepper_context\(", src)) == 0 and len(re.findall(r"\b_stepper_context\(", src)) == 6
+
+
 def kernel_resources():
     """{demangled kernel name: {vgpr, agpr, scratch, occupancy, lds, dynamic_stack}} from the <unit>.res records the
     Makefile keeps of every compile (-Rpass-analysis=kernel-resource-usage)."""
