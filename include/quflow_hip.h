@@ -435,6 +435,28 @@ int qf_mat2shr(qf_ctx *ctx, const void *W_host, double *omega_host, long long n_
 /* shc2mat_ / mat2shc_, quantization.py:331-396: omega is N^2 complex128 */
 int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host);
 int qf_mat2shc(qf_ctx *ctx, const void *W_host, void *omega_host);
+/* The per-degree budget of a state W (NULL: the resident state ctx->W), double precision, skew-Hermitian W, band limit
+ * 1 < Nmax <= N; needs the transforms' mode set as qf_mat2shr does (qf_basis_compute / _upload, or qf_basis_stream).  With
+ *     P = the context's Hamiltonian of W (the built-in solve, or what qf_set_hamiltonian installed),
+ *     A = (P W - (P W)^H) (1/hbar)             the advective tendency [P, W]/hbar; P and A are left in the Phalf and PW
+ *                                              buffers (qf_download_buffer),
+ *     F = the installed forcing at (P, W)      formed as qf_forcing forms it; of a stochastic forcing only the affine terms
+ *                                              a_W, a_P, a_lap enter -- the noise pattern does not, its counter is not touched,
+ *     omega, a, f = mat2shr of W, A, F band-limited to Nmax -- ONE sweep of the basis carries all three, and each has the
+ *                                              bits qf_mat2shr gives for that matrix alone,
+ * out[0][l] = Z_l = sum_m omega_lm^2,  out[1][l] = T_l = 2 sum_m omega_lm a_lm,  out[2][l] = I_l = 2 sum_m omega_lm f_lm
+ * (zeros without a forcing) for l < Nmax, m = -l..l.  Each sum is formed by one wavefront in a fixed order: lane t adds the
+ * products at l^2 + t, l^2 + t + 64, ... in ascending order, then the xor butterfly 32, 16, .., 1 joins the 64 lanes; the
+ * results are reproducible from run to run.  sum_l Z_l / 2 is the enstrophy, sum_l Z_l / (l (l+1)) / 2 the energy.
+ * coeffs: NULL, or [3][Nmax^2] for omega, a, f (f zeros without a forcing).
+ * Only per-iteration scratch of the context is written (the staging matrices and the transforms' staging; the device
+ * copy of the coefficients then holds omega): the state, the increment, what is installed and the stochastic counter stay,
+ * and a resident run continues bit for bit as if the call had not happened.  QF_ERR_INVALID (before anything is launched)
+ * for a bad argument or a slab budget too small for block 0; QF_ERR_STATE without a basis in resident mode, and for
+ * W_host == NULL on a context that holds a complex64 state only. */
+int qf_spectral_budget(qf_ctx *ctx, const void *W_host, int Nmax, double *out, double *coeffs);
+/* Z_l alone, l < Nmax: the same route with the state as its only column -- no solve, no product, Nmax doubles come back. */
+int qf_degree_spectrum(qf_ctx *ctx, const void *W_host, int Nmax, double *Z);
 /* shc2fun / shr2fun (quflow/transforms.py:220-268, 422-438) at bandwidth L (1..8192, independent of ctx->N):
  * MW grid (L, 2L-1), row-major.  omega_host == NULL: the coefficients the last qf_mat2shr left on ctx
  * (as qf_shr2mat's NULL).  omega is trimmed or zero-padded to L^2 entries (qf_shr2fun: after dropping a last degree

@@ -154,6 +154,8 @@ SIGNATURES = {
     "qf_mat2shr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_longlong]),
     "qf_shc2mat": (ctypes.c_int, [_vp, _vp, _vp]),
     "qf_mat2shc": (ctypes.c_int, [_vp, _vp, _vp]),
+    "qf_spectral_budget": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp]),
+    "qf_degree_spectrum": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp]),
     "qf_shr2fun": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_shc2fun": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_fun2shc": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),

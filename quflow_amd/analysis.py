@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from . import laplacian as _laplacian
+from .context import ptr
 from .laplacian import solve_poisson
 from .quantization import mat2shr, ind2elm
 from .sht import as_shr
@@ -78,6 +79,115 @@ def enstrophy_spectrum(data):
     """(el, enstrophy) with enstrophy[el-1] = sum_m omega_lm^2 (quflow/analysis.py:58-75)."""
     N, sums = _degree_sums(as_shr(data))
     return np.arange(1, N), sums
+
+
+def _band_limit(N, lmax):
+    """The band limit Nmax (degrees l < Nmax) of a budget call: N, or `lmax` in (1, N]."""
+    if lmax is None:
+        return int(N)
+    if isinstance(lmax, (bool, np.bool_)) or int(lmax) != lmax:
+        raise ValueError("lmax must be an integer in (1, N], got %r" % (lmax,))
+    if not 1 < int(lmax) <= N:
+        raise ValueError("lmax must lie in (1, N] = (1, %d], got %d" % (N, int(lmax)))
+    return int(lmax)
+
+
+def _budget_dict(rows, has_forcing, strang_splitting=None, coeffs=None):
+    """The budget's dictionary from the device's rows (3, Nmax) = Z_l, T_l, I_l, l = 0..Nmax-1: host arithmetic only.
+    Everything is reported for el = 1..Nmax-1 (as the spectra of this module); an energy form divides the enstrophy
+    quantity by el (el + 1), a flux is minus the running sum of its transfer, and the dissipation of a
+    ViscDampStep(nu, alpha) is -2 (nu el (el+1) + alpha) Z_l."""
+    rows = np.asarray(rows, dtype=np.float64)
+    nmax = rows.shape[1]
+    el = np.arange(1, nmax)
+    ll = (el * (el + 1)).astype(np.float64)
+    Z, T = rows[0, 1:].copy(), rows[1, 1:].copy()
+    out = {"el": el, "enstrophy": Z, "energy": Z / ll,
+           "enstrophy_transfer": T, "energy_transfer": T / ll}
+    out["enstrophy_flux"] = -np.cumsum(out["enstrophy_transfer"])
+    out["energy_flux"] = -np.cumsum(out["energy_transfer"])
+    if has_forcing:
+        out["enstrophy_input"] = rows[2, 1:].copy()
+        out["energy_input"] = out["enstrophy_input"] / ll
+    if strang_splitting is not None:
+        out["enstrophy_dissipation"] = -2 * (strang_splitting.nu * ll + strang_splitting.alpha) * Z
+        out["energy_dissipation"] = out["enstrophy_dissipation"] / ll
+    if coeffs is not None:
+        out["coefficients"] = {"omega": coeffs[0], "tendency": coeffs[1]}
+        if has_forcing:
+            out["coefficients"]["forcing"] = coeffs[2]
+    return out
+
+
+def _check_budget_mode(what):
+    from . import integrators
+    if not (integrators._SKEW_HERM_ and _laplacian._SKEW_HERM_):
+        raise NotImplementedError("%s needs the skew-Hermitian mode (select_skewherm(True)): the advective tendency is "
+                                  "formed as PW - (PW)^H" % what)
+
+
+def _budget_call(ctx, W, nmax, has_forcing, strang_splitting, coefficients):
+    """qf_spectral_budget on `ctx` (its transform mode set by the caller) for the host matrix W, or None: the resident state."""
+    rows = np.zeros((3, nmax), dtype=np.float64)
+    coeffs = np.zeros((3, nmax * nmax), dtype=np.float64) if coefficients else None
+    _lib.check(ctx._lib.qf_spectral_budget(ctx.handle, None if W is None else ptr(W), nmax, ptr(rows),
+                                           None if coeffs is None else ptr(coeffs)))
+    return _budget_dict(rows, has_forcing, strang_splitting, coeffs)
+
+
+def _spectrum_call(ctx, W, N):
+    """Z_l, l = 0..N-1, of the host matrix W or (None) the resident state: qf_degree_spectrum."""
+    Z = np.zeros(N, dtype=np.float64)
+    _lib.check(ctx._lib.qf_degree_spectrum(ctx.handle, None if W is None else ptr(W), N, ptr(Z)))
+    return Z
+
+
+def spectral_budget(W, hamiltonian=None, forcing=None, strang_splitting=None, lmax=None, coefficients=False, streamed=None):
+    """The per-degree budget of the state W on the device, from ONE sweep of the quantization basis (qf_spectral_budget).
+
+    With P = hamiltonian(W) (the built-in solve_poisson, or a TridiagonalHamiltonian installed for the call), the
+    advective tendency A = [P, W]/hbar and F = forcing(P, W) (an AffineForcing installed for the call), and omega, a, f =
+    mat2shr of W, A, F band-limited to degrees el < lmax (default N), the result is a dict for el = 1..lmax-1:
+
+        el                                       the degrees
+        enstrophy, energy                        Z_l = sum_m omega_lm^2 and Z_l / (el (el+1))
+        enstrophy_transfer, energy_transfer      T_l = 2 sum_m omega_lm a_lm and T_l / (el (el+1))
+        enstrophy_flux, energy_flux              -cumsum of the transfers
+        enstrophy_input, energy_input            I_l = 2 sum_m omega_lm f_lm and its energy form (with a forcing)
+        enstrophy_dissipation, energy_dissipation  -2 (nu el (el+1) + alpha) Z_l and its energy form (with
+                                                 strang_splitting=ViscDampStep(nu, alpha); host arithmetic)
+        coefficients                             {"omega", "tendency", "forcing"} (coefficients=True): each equals
+                                                 mat2shr of that matrix bit for bit
+
+    sum(enstrophy)/2 is the enstrophy and sum(energy)/2 the Euler energy of W (el = 0 carries none for a traceless state);
+    sum(enstrophy_transfer) vanishes to rounding for any Hamiltonian, sum(energy_transfer) for the built-in one.
+    complex128 W in skew-Hermitian mode; `streamed` as in mat2shr."""
+    from .context import as_c128
+    from .quantization import _transform_context
+    from .integrators import _is_native_hamiltonian, _hamiltonian_on, _forcing_on
+    Wa = np.asarray(W)
+    if Wa.dtype == np.complex64:
+        raise NotImplementedError("spectral_budget of a complex64 W: the budget is double only; convert to complex128")
+    Wc = as_c128(Wa, "W")
+    N = Wc.shape[0]
+    nmax = _band_limit(N, lmax)
+    _check_budget_mode("spectral_budget")
+    ham = None
+    if isinstance(hamiltonian, _laplacian.TridiagonalHamiltonian) and _laplacian.installable(hamiltonian):
+        hamiltonian.check_size(N)
+        ham = hamiltonian
+    elif not _is_native_hamiltonian(hamiltonian):
+        raise TypeError("spectral_budget takes the built-in Hamiltonian or a TridiagonalHamiltonian")
+    if forcing is not None:
+        if not isinstance(forcing, _laplacian.AffineForcing):
+            raise TypeError("spectral_budget takes an AffineForcing (a StochasticForcing's affine terms: on the "
+                            "DeviceTrajectory that carries it)")
+        forcing.check_size(N)
+    if strang_splitting is not None and not isinstance(strang_splitting, _laplacian.ViscDampStep):
+        raise TypeError("spectral_budget takes strang_splitting=ViscDampStep(nu, alpha) for the dissipation")
+    ctx = _transform_context(N, None, streamed)
+    with _hamiltonian_on(ctx, ham), _forcing_on(ctx, forcing):
+        return _budget_call(ctx, Wc, nmax, forcing is not None, strang_splitting, coefficients)
 
 
 def _degrees(n):

@@ -300,6 +300,7 @@ int qf_upload_W(qf_ctx *ctx, const void *W_host)
     QF_HIP(hipMemcpyAsync(ctx->W, W_host, (size_t)ctx->N * ctx->N * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->w_skew_known = false;
+    ctx->w_c128_set = true;
     return QF_OK;
 }
 

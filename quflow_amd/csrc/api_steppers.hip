@@ -574,6 +574,7 @@ int qf_states_select(qf_ctx *ctx, int j)
     const size_t mbytes = (size_t)ctx->N * ctx->N * sizeof(cplx);
     QF_HIP(hipMemcpyAsync(ctx->W, ctx->stack[5 * j], mbytes, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->w_skew_known = false;       // (as after qf_upload_W)
+    ctx->w_c128_set = true;
     ctx->increment_valid = false;
     return QF_OK;
 }

@@ -149,6 +149,7 @@ int qf_shr2mat(qf_ctx *ctx, const double *omega_host, long long n_omega, void *W
     if (!W_host) {       // the resident state is replaced: as after qf_rotate(NULL), no increment is carried
         ctx->w_skew_known = false;
         ctx->increment_valid = false;
+        ctx->w_c128_set = true;
     }
     QF_TRY(qf_launch_shr2mat(ctx, Nmax, ctx->sh_omega, dst));
     if (W_host) QF_HIP(hipMemcpyAsync(W_host, dst, (size_t)NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
@@ -199,6 +200,7 @@ int qf_shc2mat(qf_ctx *ctx, const void *omega_host, void *W_host)
     if (!W_host) {       // the resident state is replaced: as after qf_rotate(NULL), no increment is carried
         ctx->w_skew_known = false;
         ctx->increment_valid = false;
+        ctx->w_c128_set = true;
     }
     QF_TRY(qf_launch_shc2mat(ctx, ctx->sh_omega, dst));
     if (W_host) QF_HIP(hipMemcpyAsync(W_host, dst, NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
@@ -225,6 +227,89 @@ int qf_mat2shc(qf_ctx *ctx, const void *W_host, void *omega_host)
     QF_HIP(hipMemcpyAsync(omega_host, ctx->sh_omega, NN * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));
     return QF_OK;
+}
+
+// ---- the per-degree budget of a state (include/quflow_hip.h): Z_l, T_l, I_l from one sweep of the basis
+// nv = 1: the spectrum alone (no solve, no product); 2: with the advective tendency; 3: with the installed forcing too.
+// Where everything lives (all of it per-iteration scratch, free between stepper calls):
+//   W       ctx->W (resident) or ctx->stage (uploaded)            -X^H, then F  ctx->Whalf
+//   P, A    ctx->Phalf, ctx->PW, both left there for qf_download_buffer
+//   packed diagonals  ctx->sh_stage parts 0..2;   z_0  part 3;   z_1, z_2  ctx->Whalf, ctx->stage (dead once packed)
+//   omega, a  ctx->sh_omega (two halves);   f, the sums  ctx->sh_stage parts 0, 1 (dead after the sweep)
+static int budget_run(qf_ctx *ctx, const char *who, const void *W_host, int Nmax, int nv, double *out, double *coeffs)
+{
+    QF_TRY(check_ctx(ctx));
+    const int N = ctx->N;
+    if (!out) {
+        qf_set_error("%s: null output", who);
+        return QF_ERR_INVALID;
+    }
+    if (Nmax <= 1 || Nmax > N) {
+        qf_set_error("%s: band limit Nmax=%d outside 2..N=%d", who, Nmax, N);
+        return QF_ERR_INVALID;
+    }
+    if (!W_host && ctx->c64 && !ctx->w_c128_set) {
+        qf_set_error("%s: this context holds a complex64 state only; the budget is double precision (pass W_host)", who);
+        return QF_ERR_STATE;
+    }
+    if (ctx->slab_budget > 0) {       // (the slab plan's refusal comes before anything is launched)
+        std::vector<int> first;
+        long long need = 0;
+        QF_TRY(qf_slab_plan(N, Nmax, ctx->slab_budget, first, &need));
+    }
+    QF_TRY(need_source(ctx, who));
+    const size_t NN = (size_t)N * N, half = (size_t)N * (N + 1) / 2;
+    const cplx *W = ctx->W;
+    if (W_host) {
+        QF_HIP(hipMemcpyAsync(ctx->stage, W_host, NN * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+        W = ctx->stage;
+    }
+    if (nv >= 2) {
+        const double inv_hb = 1.0 / qf_hbar(N);
+        QF_TRY(qf_launch_hamiltonian(ctx, W, ctx->Phalf, 1.0));                                    // P
+        QF_TRY(qf_launch_zgemm(ctx, ctx->Phalf, W, ctx->PW, nullptr));                             // X = P @ W
+        QF_TRY(qf_launch_neg_conj_transpose(ctx, ctx->PW, ctx->Whalf));                            // -X^H
+        QF_TRY(qf_launch_lincomb(ctx, 1.0, ctx->PW, 1.0, ctx->Whalf, 0.0, ctx->PW));               // X - X^H
+        QF_TRY(qf_launch_lincomb(ctx, inv_hb, ctx->PW, 0.0, (const cplx *)nullptr, 0.0, ctx->PW)); // A = (X - X^H) (1/hbar)
+    }
+    if (nv == 3) {
+        // the affine terms only: a stochastic forcing's pattern belongs to a step (qf_forcing), and its counter stays
+        const bool f0 = ctx->forcing_f0_on;
+        if (ctx->stoch.on) ctx->forcing_f0_on = false;
+        const int rc = qf_launch_forcing_affine(ctx, ctx->Phalf, W, ctx->Whalf, 1.0, 1.0);
+        ctx->forcing_f0_on = f0;
+        QF_TRY(rc);
+    }
+    const cplx *mats[3] = {W, ctx->PW, ctx->Whalf};
+    cplx *z[3] = {ctx->sh_stage + 3 * half, ctx->Whalf, ctx->stage};
+    double *omega[3] = {ctx->sh_omega, ctx->sh_omega + NN, reinterpret_cast<double *>(ctx->sh_stage)};
+    double *sums = reinterpret_cast<double *>(ctx->sh_stage + half);
+    ctx->sh_shr_count = 0;
+    QF_TRY(qf_launch_degree_budget(ctx, Nmax, nv, mats, z, omega, sums));
+    const size_t LL = (size_t)Nmax * Nmax;
+    QF_HIP(hipMemcpyAsync(out, sums, (size_t)nv * Nmax * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    for (int v = 0; coeffs && v < nv; ++v)
+        QF_HIP(hipMemcpyAsync(coeffs + v * LL, omega[v], LL * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->sh_shr_count = (long long)LL;     // ctx->sh_omega starts with mat2shr of the state, band-limited to Nmax
+    return QF_OK;
+}
+
+int qf_spectral_budget(qf_ctx *ctx, const void *W_host, int Nmax, double *out, double *coeffs)
+{
+    const int nv = (ctx && ctx->forcing_on) ? 3 : 2;
+    QF_TRY(budget_run(ctx, "qf_spectral_budget", W_host, Nmax, nv, out, coeffs));
+    if (nv == 2) {      // no forcing: I = 0, f = 0
+        const size_t LL = (size_t)Nmax * Nmax;
+        for (int l = 0; l < Nmax; ++l) out[2 * (size_t)Nmax + l] = 0.0;
+        for (size_t i = 0; coeffs && i < LL; ++i) coeffs[2 * LL + i] = 0.0;
+    }
+    return QF_OK;
+}
+
+int qf_degree_spectrum(qf_ctx *ctx, const void *W_host, int Nmax, double *Z)
+{
+    return budget_run(ctx, "qf_degree_spectrum", W_host, Nmax, 1, Z, nullptr);
 }
 
 // ---- spherical-harmonic synthesis (quflow/transforms.py:220-268, 422-438; kernels in sht.hip) ----------------

@@ -373,6 +373,8 @@ struct qf_ctx {
     cplx *W = nullptr;       // vorticity state
     bool w_skew_known = false;     // W[j,i] == -conj(W[i,j]) exactly: verified at the entry of a qf_isomp call and
                                    // kept by every isomp update (W += 2 (PW - PW^H)); cleared by whatever else writes W
+    bool w_c128_set = false;       // a complex128 state has been put into W (qf_upload_W, qf_shr2mat / qf_shc2mat into the state,
+                                   // qf_states_select): what tells a context that holds a complex64 state only
     cplx *dW[2] = {nullptr, nullptr};  // iteration vector, ping-pong (cur / new)
     int dw_cur = 0;
     bool increment_is_zero = true; // this call starts from dW = 0 (not a qf_isomp_continue)
@@ -676,6 +678,14 @@ int qf_launch_band_basis(qf_ctx *ctx, int Nmax, double *band_dev);
 // column arithmetic of qf_launch_shr2mat's streamed form, hence its bits.
 int qf_launch_band_shr2mat(qf_ctx *ctx, int Nmax, const double *band_dev, const double *omega_dev, cplx *stage, cplx *W_dev);
 int qf_launch_mat2shr(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev);
+// The spectral budget's transform stage: omega[v] = mat2shr(mats[v]) band-limited to Nmax for v < nv (1..3) in ONE sweep of
+// the basis (resident or slab by slab), each with the bits of qf_launch_mat2shr alone, then sums_dev[r * Nmax + l] =
+// c_r sum_{|m| <= l} omega[0][l,m] omega[r][l,m], c = (1, 2, 2), for r < nv.  The packed diagonals go to ctx->sh_stage
+// (three of its four parts); z[v] (>= N(N+1)/2 complex each), omega[v] (>= Nmax^2 doubles each) and sums_dev are the
+// caller's and disjoint: z may overlay the matrices (dead once packed) but not the packed diagonals; omega and sums may
+// overlay the packed diagonals too (dead after the sweep).
+int qf_launch_degree_budget(qf_ctx *ctx, int Nmax, int nv, const cplx *const mats[3], cplx *const z[3], double *const omega[3],
+                            double *sums_dev);
 int qf_launch_shc2mat(qf_ctx *ctx, const double *omega_dev, cplx *W_dev);
 int qf_launch_mat2shc(qf_ctx *ctx, const cplx *W_dev, double *omega_dev);
 

@@ -18,6 +18,11 @@
 //                    row-coalesced 512-byte loads of B, wavefront-shuffle reductions;
 //   k_block_vecmat : 64 columns of B_m per workgroup, the four waves split the rows, B read in
 //                    512-byte row segments, d_m broadcast from LDS, partial sums combined in LDS.
+// The spectral budget (qf_spectral_budget: Z_l, T_l, I_l per degree) needs mat2shr of up to three matrices -- the state,
+// its advective tendency, the forcing -- and pays ONE sweep for them: k_block_vecmat_multi carries all their packed
+// diagonals through the row loop k_block_vecmat runs (block_vecmat_rows, written once), so each entry of the basis is
+// read once and every coefficient column keeps the bits of mat2shr alone; k_degree_sums then reduces the products
+// omega_lm v_lm over m, one wavefront per degree.
 #include "qf_internal.h"
 
 #pragma clang fp contract(off)   // the table of the direct Laplacian follows the reference's op order
@@ -328,15 +333,26 @@ __global__ void k_pack_diags(int N, int Nmax, const cplx *__restrict__ W, cplx *
 }
 
 // ---- z_m[j] = sum_k d_m[k] B_m[k, j], j < J; blocks m0 + blockIdx.y
-template <int MODE, bool SLAB>
-__global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, int m0, const double *__restrict__ basis,
-                                                       const cplx *__restrict__ d0, const cplx *__restrict__ d1,
-                                                       cplx *__restrict__ z0, cplx *__restrict__ z1)
+// The packed diagonals and results of the NV vectors one sweep carries (mat2shc: lower and upper diagonal; the spectral
+// budget: the state, its advective tendency and the forcing).  Passed by value: indexed by unrolled constants only.
+template <int NV>
+struct vecmat_vectors {
+    const cplx *d[NV];
+    cplx *z[NV];
+};
+
+// The row loop, written once for every kernel that sweeps B_m from the left.  Each entry of B is read once and multiplied
+// into all NV vectors; vectors v >= nload are not loaded (their d counts as zero: mat2shc's upper diagonal at m = 0).
+// The accumulation order of a vector depends on the row and column indices alone -- wave w takes the rows w, w + 4, ... of
+// every 256-row chunk in ascending order, then (wave 0 + wave 1) + (wave 2 + wave 3) -- never on NV or on the other
+// vectors, so every column has the bits it has when it is swept alone.
+template <int NV, bool SLAB>
+__device__ __forceinline__ void block_vecmat_rows(int N, int Nmax, int m0, const double *__restrict__ basis,
+                                                  const vecmat_vectors<NV> &p, int m, int nload)
 {
-    constexpr int NV = (MODE == MODE_SHC) ? 2 : 1, KCH = 256;
+    constexpr int KCH = 256;
     __shared__ cplx ds[NV][KCH];
     __shared__ double part[4][NV][2][64];
-    const int m = m0 + blockIdx.y;
     const int n = N - m;
     const int J = Nmax - m;
     const int j0 = blockIdx.x * 64;
@@ -354,13 +370,12 @@ __global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, int m0, c
         __syncthreads();
         {
             const int k = k0 + threadIdx.x;
-            cplx a = make_double2(0.0, 0.0), b = a;
-            if (k < n) {
-                a = d0[dof + k];
-                if (NV == 2 && m != 0) b = d1[dof + k];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                cplx a = make_double2(0.0, 0.0);
+                if (k < n && v < nload) a = p.d[v][dof + k];
+                ds[v][threadIdx.x] = a;
             }
-            ds[0][threadIdx.x] = a;
-            if (NV == 2) ds[NV - 1][threadIdx.x] = b;
         }
         __syncthreads();
         const int kend = (n - k0 < KCH) ? n - k0 : KCH;
@@ -397,9 +412,32 @@ __global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, int m0, c
         for (int v = 0; v < NV; ++v) {
             const double re = (part[0][v][0][lane] + part[1][v][0][lane]) + (part[2][v][0][lane] + part[3][v][0][lane]);
             const double im = (part[0][v][1][lane] + part[1][v][1][lane]) + (part[2][v][1][lane] + part[3][v][1][lane]);
-            (v == 0 ? z0 : z1)[dof + j] = make_double2(re, im);
+            p.z[v][dof + j] = make_double2(re, im);
         }
     }
+}
+
+template <int MODE, bool SLAB>
+__global__ __launch_bounds__(256) void k_block_vecmat(int N, int Nmax, int m0, const double *__restrict__ basis,
+                                                       const cplx *__restrict__ d0, const cplx *__restrict__ d1,
+                                                       cplx *__restrict__ z0, cplx *__restrict__ z1)
+{
+    constexpr int NV = (MODE == MODE_SHC) ? 2 : 1;
+    vecmat_vectors<NV> p;
+    p.d[0] = d0;
+    p.z[0] = z0;
+    p.d[NV - 1] = (NV == 2) ? d1 : d0;
+    p.z[NV - 1] = (NV == 2) ? z1 : z0;
+    const int m = m0 + blockIdx.y;
+    block_vecmat_rows<NV, SLAB>(N, Nmax, m0, basis, p, m, (NV == 2 && m == 0) ? 1 : NV);
+}
+
+// ---- the same sweep for NV packed diagonals of NV different matrices (mat2shr of each of them in one pass over the basis)
+template <int NV, bool SLAB>
+__global__ __launch_bounds__(256) void k_block_vecmat_multi(int N, int Nmax, int m0, const double *__restrict__ basis,
+                                                             vecmat_vectors<NV> p)
+{
+    block_vecmat_rows<NV, SLAB>(N, Nmax, m0, basis, p, m0 + blockIdx.y, NV);
 }
 
 // ---- m-major results z -> omega with the convention factors
@@ -435,6 +473,33 @@ __global__ void k_unpack_coeffs(int N, int Nmax, const cplx *__restrict__ z0, co
             oc[el * el + el - m] = make_double2((sgn * b.y) * invN, -(sgn * b.x) * invN);
         }
     }
+}
+
+// ---- per-degree sums of products of real coefficient arrays: out[r * Nmax + l] = sum_{m=-l..l} u[l^2+l+m] v_r[l^2+l+m]
+// for l < Nmax, r = blockIdx.y (the rows Z, T/2, I/2 of the spectral budget: v_0 = u).  One wavefront per degree, four
+// degrees per workgroup.  The order is fixed: lane t sums the entries l^2 + t, l^2 + t + 64, ... of the degree in
+// ascending order (product and sum rounded separately), then the xor butterfly 32, 16, 8, 4, 2, 1 over the 64 lanes.
+// `scale` (1 or 2) multiplies the finished sum, which is exact.
+struct degree_rows {
+    const double *v[3];
+    double scale[3];
+};
+__global__ __launch_bounds__(256) void k_degree_sums(int Nmax, const double *__restrict__ u, degree_rows rows,
+                                                      double *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (l >= Nmax) return;                    // (whole wavefronts leave: the shuffles below see all 64 lanes)
+    const int r = blockIdx.y;
+    const double *__restrict__ v = r == 0 ? rows.v[0] : (r == 1 ? rows.v[1] : rows.v[2]);
+    const double sc = r == 0 ? rows.scale[0] : (r == 1 ? rows.scale[1] : rows.scale[2]);
+    const size_t base = (size_t)l * l;
+    const int count = 2 * l + 1;
+    double s = 0.0;
+    for (int t = lane; t < count; t += 64) s += u[base + t] * v[base + t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) out[(size_t)r * Nmax + l] = sc * s;
 }
 
 // The streamed form's slabs for band limit Nmax, planned and the slab grown to the largest of them (hipFree waits for the
@@ -520,7 +585,71 @@ int backward(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_dev)
     return QF_OK;
 }
 
+template <int NV, bool SLAB>
+void launch_vecmat_multi(qf_ctx *ctx, dim3 grid, int Nmax, int m0, const double *basis, cplx *const d[3], cplx *const z[3])
+{
+    vecmat_vectors<NV> p;
+    for (int v = 0; v < NV; ++v) {
+        p.d[v] = d[v];
+        p.z[v] = z[v];
+    }
+    hipLaunchKernelGGL((k_block_vecmat_multi<NV, SLAB>), grid, dim3(256), 0, ctx->stream, ctx->N, Nmax, m0, basis, p);
+}
+
+template <bool SLAB>
+int vecmat_multi(qf_ctx *ctx, int nv, dim3 grid, int Nmax, int m0, const double *basis, cplx *const d[3], cplx *const z[3])
+{
+    // one vector: mat2shr's own kernel
+    if (nv == 1)
+        hipLaunchKernelGGL((k_block_vecmat<MODE_SHR, SLAB>), grid, dim3(256), 0, ctx->stream, ctx->N, Nmax, m0, basis, d[0],
+                           (const cplx *)nullptr, z[0], (cplx *)nullptr);
+    else if (nv == 2) launch_vecmat_multi<2, SLAB>(ctx, grid, Nmax, m0, basis, d, z);
+    else launch_vecmat_multi<3, SLAB>(ctx, grid, Nmax, m0, basis, d, z);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
 }  // namespace
+
+// mat2shr of nv matrices in ONE sweep of the basis, then the per-degree sums of omega_0 * omega_r.  The diagonals are
+// packed and the coefficients unpacked by mat2shr's own kernels, launched once per matrix (two N^2-sized passes per matrix
+// beside a sweep of N^3/3): with the shared row loop every omega_r has the bits of qf_launch_mat2shr of that matrix alone.
+int qf_launch_degree_budget(qf_ctx *ctx, int Nmax, int nv, const cplx *const mats[3], cplx *const z[3], double *const omega[3],
+                            double *sums_dev)
+{
+    const int N = ctx->N;
+    const size_t half = (size_t)N * (N + 1) / 2;
+    cplx *d[3] = {ctx->sh_stage, ctx->sh_stage + half, ctx->sh_stage + 2 * half};
+    std::vector<int> first;
+    if (ctx->slab_budget > 0) QF_TRY(reserve_slabs(ctx, Nmax, first));
+    dim3 gp((N + 255) / 256, Nmax);
+    for (int v = 0; v < nv; ++v) {
+        hipLaunchKernelGGL(k_pack_diags<MODE_SHR>, gp, dim3(256), 0, ctx->stream, N, Nmax, mats[v], d[v], (cplx *)nullptr);
+        QF_HIP(hipGetLastError());
+    }
+    if (ctx->slab_budget == 0) {
+        QF_TRY(vecmat_multi<false>(ctx, nv, dim3((Nmax + 63) / 64, Nmax), Nmax, 0, ctx->basis, d, z));
+    } else {
+        for (size_t s = 0; s + 1 < first.size(); ++s) {
+            const int m0 = first[s], m1 = first[s + 1];
+            QF_TRY(generate_slab(ctx, Nmax, m0, m1));
+            QF_TRY(vecmat_multi<true>(ctx, nv, dim3((Nmax - m0 + 63) / 64, m1 - m0), Nmax, m0, ctx->slab, d, z));
+        }
+    }
+    dim3 gu((Nmax + 255) / 256, Nmax);
+    degree_rows rows;
+    for (int v = 0; v < 3; ++v) {
+        rows.v[v] = omega[v < nv ? v : 0];
+        rows.scale[v] = v == 0 ? 1.0 : 2.0;
+    }
+    for (int v = 0; v < nv; ++v) {
+        hipLaunchKernelGGL(k_unpack_coeffs<MODE_SHR>, gu, dim3(256), 0, ctx->stream, N, Nmax, z[v], (const cplx *)nullptr, omega[v]);
+        QF_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_degree_sums, dim3((Nmax + 3) / 4, nv), dim3(256), 0, ctx->stream, Nmax, omega[0], rows, sums_dev);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
 
 int qf_slab_plan(int N, int Nmax, long long slab_bytes, std::vector<int> &first, long long *max_bytes)
 {

@@ -1185,6 +1185,35 @@ class DeviceTrajectory:
         _lib.check(self._lib.qf_shr2fun(self.ctx.handle, None, ctypes.c_longlong(n), L, int(bool(berezin)), ptr(f)))
         return f
 
+    def spectral_budget(self, lmax=None, coefficients=False):
+        """quflow_amd.analysis.spectral_budget of the resident state with what is installed on this trajectory -- its
+        Hamiltonian, its forcing (of a StochasticForcing only the affine terms a_W, a_P, a_lap: the noise pattern belongs
+        to a step and does not enter, the counter is not touched), the dissipation of its ViscDampStep -- from one sweep of
+        the basis; 3 lmax doubles cross PCIe (and the coefficients when asked).  The state, the carried increment and the
+        statistics of the run are untouched: the next `advance` continues bit for bit as if the call had not happened."""
+        from . import analysis
+        self._double_only("spectral_budget")
+        nmax = analysis._band_limit(self.N, lmax)
+        analysis._check_budget_mode("spectral_budget")
+        self._need_basis()
+        return analysis._budget_call(self.ctx, None, nmax, self.forcing is not None, self.strang_splitting, coefficients)
+
+    def _degree_spectrum(self, what):
+        from . import analysis
+        self._double_only(what)
+        self._need_basis()
+        return np.arange(1, self.N), analysis._spectrum_call(self.ctx, None, self.N)[1:]
+
+    def enstrophy_spectrum(self):
+        """(el, enstrophy) of the resident state as quflow_amd.analysis.enstrophy_spectrum gives it, summed per degree on
+        the device (qf_degree_spectrum: no solve, no product): N doubles cross PCIe instead of the N^2 of `shr()`."""
+        return self._degree_spectrum("enstrophy_spectrum")
+
+    def energy_spectrum(self, beta=0):
+        """(el, energy) of the resident state as quflow_amd.analysis.energy_spectrum gives it, from the same sums."""
+        el, Z = self._degree_spectrum("energy_spectrum")
+        return el, Z / (el * (el + 1)) ** (1 - beta / 2)
+
     def spectrum(self):
         """The ascending eigenvalues of -i W for the resident state: the invariant of the isospectral flow, by the
         device eigensolver (qf_eigh_state, quflow_amd.linalg).  Only the N eigenvalues cross PCIe."""
@@ -1332,6 +1361,10 @@ class DeviceStackTrajectory:
     def fun(self, j, n_omega=None, berezin=True):
         """DeviceTrajectory.fun of member j."""
         return self._select(j).fun(n_omega, berezin)
+
+    def spectral_budget(self, j, lmax=None, coefficients=False):
+        """DeviceTrajectory.spectral_budget of member j (the built-in Hamiltonian, no forcing)."""
+        return self._select(j).spectral_budget(lmax, coefficients)
 
     def spectrum(self, j):
         """DeviceTrajectory.spectrum of member j: the invariant of the flow for every member of the stack."""
