@@ -341,6 +341,30 @@ int qf_mhd_diagnostics(qf_ctx *ctx, double out[5]);
  * call's closing synchronisation.  Same results as the two calls.  mhd_out == NULL: qf_states_advance. */
 int qf_states_advance_diag(qf_ctx *ctx, double dt, int steps, double tol, int minit, int maxit, int reinitialize, int magnetic,
                            qf_isomp_stats *stats_out, double *mhd_out);
+/* The per-degree budget of the resident MHD pair (W, Theta), k == 2, of the built-in system (mhd.py:10-18, 361-393):
+ *     P = Delta^-1 W,  B = Delta Theta,   W' = ([P, W] + [B, Theta]) / hbar,   Theta' = [P, Theta] / hbar.
+ * Band limit 1 < Nmax <= N; the transforms' mode set as for qf_mat2shr (qf_basis_compute / _upload, or qf_basis_stream).
+ * Each bracket is formed as qf_spectral_budget forms its tendency, (X Y - (X Y)^H) (1/hbar) with one plain product, and
+ *     omega, theta, a, b, c = mat2shr of W, Theta, [P,W]/hbar, [B,Theta]/hbar, [P,Theta]/hbar band-limited to Nmax
+ * come from ONE sweep of the basis that carries all five; each has the bits qf_mat2shr gives for that matrix alone.
+ * out[r][l], l < Nmax, is scale_r sum_{m=-l..l} u_lm v_lm, summed in the order qf_spectral_budget fixes:
+ *     r      0            1            2            3          4          5          6        7        8
+ *     u v    omega omega  theta theta  omega theta  omega a    omega b    theta c    theta a  theta b  omega c
+ *     scale  1            1            1            2          2          2          1        1        1
+ * With ll = l (l + 1): out[0]/ll and ll out[1] are the kinetic and magnetic energy spectra (their sums over l, halved, are
+ * qf_mhd_diagnostics' Ek and Em), out[1] the mean-square potential, out[2] the cross helicity; out[3]/ll, out[4]/ll and
+ * ll out[5] the kinetic transfer by advection, by the Lorentz term, and the magnetic transfer; out[6] + out[7] + out[8]
+ * the transfer of cross helicity.  coeffs: NULL, or [5][Nmax^2] for omega, theta, a, b, c.
+ * P, B and the three tendency matrices stay readable (qf_download_buffer, QF_BUF_MHD_*) until the next such call.
+ * The call reads the two members of the stack and writes buffers of its own (allocated on the first call, about
+ * 10 N^2 complex128, freed with the context), the staging matrices Whalf and PW, and in streamed mode the slab: the
+ * stack, its increments, the state W of the context, the device copy of the coefficients (what qf_mat2shr left for
+ * qf_shr2mat / qf_shr2fun) and the transforms' staging are left as they were, and a resident run continues bit for bit as
+ * if the call had not happened.
+ * QF_ERR_STATE without a resident stack, and without a basis in resident mode; QF_ERR_INVALID for k != 2, a null `out`,
+ * Nmax outside 2..N or a slab budget too small for block 0; QF_ERR_UNSUPPORTED while a forcing or a Hamiltonian is
+ * installed on the context (the system above is the built-in one) -- each before anything is launched. */
+int qf_mhd_spectral_budget(qf_ctx *ctx, int Nmax, double *out, double *coeffs);
 
 /* ---- the stepper with HOST HOOKS: isomp_fixedpoint's `forcing`, foreign `hamiltonian`, `strang_splitting`,
  *      `callback` (isospectral.py:338-353, 403-423, 466-467, 488-492, 512-520, 547-551, 598-603), the
@@ -579,6 +603,12 @@ int qf_timer_stop(qf_ctx *ctx, double *elapsed_ms);
 #define QF_BUF_WHALF 2
 #define QF_BUF_PHALF 3
 #define QF_BUF_PW 4
+/* what the last qf_mhd_spectral_budget left: P, B and the three tendencies (QF_ERR_STATE before the first such call) */
+#define QF_BUF_MHD_P 5
+#define QF_BUF_MHD_B 6
+#define QF_BUF_MHD_ADVECTION 7
+#define QF_BUF_MHD_LORENTZ 8
+#define QF_BUF_MHD_INDUCTION 9
 int qf_download_buffer(qf_ctx *ctx, int which, void *host);
 /* Guard zones around every device allocation of the library (QUFLOW_HIP_DEBUG_GUARD=1 in the environment when the process
  * starts; csrc/guard.hip): reads back the zones of every live allocation and reports how many allocations were made under

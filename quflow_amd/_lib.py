@@ -24,6 +24,8 @@ ERR_NAMES = {1: "QF_ERR_INVALID", 2: "QF_ERR_NO_DEVICE", 3: "QF_ERR_HIP", 4: "QF
 KERNEL_IDS = {"poisson": 0, "gemm1": 1, "gemm2": 2, "norm": 3, "update": 4, "slice": 5}
 ERK_METHODS = {"euler": 0, "heun": 1, "rk4": 2}
 BUFFER_IDS = {"W": 0, "dW": 1, "Whalf": 2, "Phalf": 3, "PW": 4}
+# what the last qf_mhd_spectral_budget left (QF_BUF_MHD_*: buffers of that call's own, QF_ERR_STATE before its first run)
+MHD_BUFFER_IDS = {"P": 5, "B": 6, "advection": 7, "lorentz": 8, "induction": 9}
 
 
 class QuflowHipError(RuntimeError):
@@ -137,6 +139,7 @@ SIGNATURES = {
     "qf_states_select": (ctypes.c_int, [_vp, ctypes.c_int]),
     "qf_states_store": (ctypes.c_int, [_vp, ctypes.c_int]),
     "qf_mhd_diagnostics": (ctypes.c_int, [_vp, _dp]),
+    "qf_mhd_spectral_budget": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     "qf_states_inner": (ctypes.c_int, [_vp, _dp]),
     "qf_isomp_hooked": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(IsompHooks),

@@ -190,6 +190,94 @@ def spectral_budget(W, hamiltonian=None, forcing=None, strang_splitting=None, lm
         return _budget_call(ctx, Wc, nmax, forcing is not None, strang_splitting, coefficients)
 
 
+MHD_COEFFICIENTS = ("omega", "theta", "advection", "lorentz", "induction")
+
+
+def _mhd_budget_dict(rows, coeffs=None):
+    """The MHD budget's dictionary from the device's rows (9, Nmax) of qf_mhd_spectral_budget, l = 0..Nmax-1: host arithmetic
+    only, in the style of `_budget_dict`.  Everything is reported for el = 1..Nmax-1; with ll = el (el + 1) the kinetic
+    forms divide by ll, the magnetic ones multiply by it, and a flux is minus the running sum of its transfer."""
+    rows = np.asarray(rows, dtype=np.float64)
+    nmax = rows.shape[1]
+    el = np.arange(1, nmax)
+    ll = (el * (el + 1)).astype(np.float64)
+    r = [rows[i, 1:].copy() for i in range(9)]
+    out = {"el": el,
+           "enstrophy": r[0], "kinetic_energy": r[0] / ll,
+           "magnetic_potential": r[1], "magnetic_energy": ll * r[1],
+           "cross_helicity": r[2],
+           "kinetic_transfer_advection": r[3] / ll, "kinetic_transfer_lorentz": r[4] / ll,
+           "magnetic_transfer": ll * r[5],
+           "enstrophy_transfer_advection": r[3], "enstrophy_source_lorentz": r[4],
+           "potential_transfer": r[5],
+           "cross_helicity_transfer": r[6] + r[7] + r[8]}
+    out["energy"] = out["kinetic_energy"] + out["magnetic_energy"]
+    out["energy_transfer"] = out["kinetic_transfer_advection"] + out["kinetic_transfer_lorentz"] + out["magnetic_transfer"]
+    for flux, transfer in (("kinetic_flux_advection", "kinetic_transfer_advection"), ("energy_flux", "energy_transfer"),
+                           ("potential_flux", "potential_transfer"), ("cross_helicity_flux", "cross_helicity_transfer"),
+                           ("enstrophy_flux_advection", "enstrophy_transfer_advection")):
+        out[flux] = -np.cumsum(out[transfer])
+    if coeffs is not None:
+        out["coefficients"] = dict(zip(MHD_COEFFICIENTS, coeffs))
+    return out
+
+
+def _mhd_budget_call(ctx, nmax, coefficients):
+    """qf_mhd_spectral_budget on `ctx` (its transform mode set by the caller) for the resident pair."""
+    rows = np.zeros((9, nmax), dtype=np.float64)
+    coeffs = np.zeros((5, nmax * nmax), dtype=np.float64) if coefficients else None
+    _lib.check(ctx._lib.qf_mhd_spectral_budget(ctx.handle, nmax, ptr(rows), None if coeffs is None else ptr(coeffs)))
+    return _mhd_budget_dict(rows, coeffs)
+
+
+def mhd_spectral_budget(state, lmax=None, coefficients=False, streamed=None):
+    """The per-degree budget of the MHD pair state = (W, Theta), a (2,N,N) complex128 array, on the device, from ONE sweep of
+    the quantization basis (qf_mhd_spectral_budget).  The system is quflow/integrators/mhd.py's with hamiltonian = solve_mhd:
+
+        P = Delta^-1 W,  B = Delta Theta,   W' = ([P, W] + [B, Theta]) / hbar,   Theta' = [P, Theta] / hbar.
+
+    With omega, theta, a, b, c = mat2shr of W, Theta, [P,W]/hbar (advection), [B,Theta]/hbar (the Lorentz term),
+    [P,Theta]/hbar (induction), band-limited to degrees el < lmax (default N), and ll = el (el + 1), the result is a dict
+    for el = 1..lmax-1 (sums over m):
+
+        el                              the degrees
+        enstrophy, kinetic_energy       sum omega^2 and the same / ll
+        magnetic_potential, magnetic_energy   sum theta^2 (the mean-square potential) and ll times it
+        energy                          kinetic_energy + magnetic_energy
+        cross_helicity                  sum omega theta
+        kinetic_transfer_advection, kinetic_transfer_lorentz   2 sum omega a / ll and 2 sum omega b / ll
+        magnetic_transfer               ll 2 sum theta c
+        energy_transfer                 the sum of those three
+        enstrophy_transfer_advection    2 sum omega a
+        enstrophy_source_lorentz        2 sum omega b: the Lorentz term does not conserve enstrophy -- a source, no flux
+        potential_transfer              2 sum theta c
+        cross_helicity_transfer         sum theta a + sum theta b + sum omega c
+        kinetic_flux_advection, energy_flux, potential_flux, cross_helicity_flux, enstrophy_flux_advection
+                                        -cumsum of the matching transfer
+        coefficients                    {"omega", "theta", "advection", "lorentz", "induction"} (coefficients=True): each
+                                        equals mat2shr of that matrix bit for bit
+
+    sum(kinetic_energy)/2, sum(magnetic_energy)/2, sum(magnetic_potential)/2, sum(cross_helicity) and sum(enstrophy)/2 are
+    energy_kinetic, energy_magnetic, magnetic_casimir, cross_helicity and enstrophy of `physics.mhd_diagnostics`.  These
+    vanish to rounding: sum(kinetic_transfer_advection), sum(kinetic_transfer_lorentz + magnetic_transfer),
+    sum(potential_transfer), sum(cross_helicity_transfer), sum(enstrophy_transfer_advection).
+    Skew-Hermitian mode; `streamed` as in mat2shr."""
+    from .quantization import _transform_context
+    state = np.asarray(state)
+    if state.dtype == np.complex64:
+        raise NotImplementedError("mhd_spectral_budget of a complex64 state: the budget is double only; convert to "
+                                  "complex128")
+    if state.ndim != 3 or state.shape[0] != 2 or state.shape[1] != state.shape[2]:
+        raise ValueError("the MHD state must be a (2,N,N) array (W, Theta), got shape %s" % (state.shape,))
+    N = state.shape[-1]
+    nmax = _band_limit(N, lmax)
+    _check_budget_mode("mhd_spectral_budget")
+    sc = np.ascontiguousarray(state, dtype=np.complex128)
+    ctx = _transform_context(N, None, streamed)
+    _lib.check(ctx._lib.qf_states_upload(ctx.handle, ptr(sc), 2))
+    return _mhd_budget_call(ctx, nmax, coefficients)
+
+
 def _degrees(n):
     """The degree l of every index below n."""
     return ind2elm(np.arange(n))[0]

@@ -228,7 +228,8 @@ int qf_ctx_destroy(qf_ctx *ctx)
     void *ptrs[] = {ctx->W, ctx->dW[0], ctx->dW[1], ctx->Whalf, ctx->Phalf, ctx->PW, ctx->kahan_c, ctx->stage,
                     ctx->lap, ctx->lap_user, ctx->poisson.tab, ctx->ham.tab, ctx->ham_offset, ctx->forcing_f0, ctx->stoch.basis, ctx->stoch.omega,
                     ctx->stoch.stage, ctx->stoch.sigma, ctx->rowpart, ctx->rowsum,
-                    ctx->t32_partial, ctx->t32_arrive, ctx->W2, ctx->Whalf2, ctx->ns_inv, ctx->ns_tmp, ctx->multi_rowpart, ctx->scalars, ctx->sk_partial, ctx->sk_flags, ctx->basis, ctx->sh_stage, ctx->sh_omega, ctx->slab};
+                    ctx->t32_partial, ctx->t32_arrive, ctx->W2, ctx->Whalf2, ctx->ns_inv, ctx->ns_tmp, ctx->multi_rowpart, ctx->scalars, ctx->sk_partial, ctx->sk_flags, ctx->basis, ctx->sh_stage, ctx->sh_omega, ctx->slab,
+                    ctx->mhdb_mats, ctx->mhdb_vec, ctx->mhdb_sums};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     void *sht[] = {ctx->sht.omega, ctx->sht.tab, ctx->sht.col, ctx->sht.At, ctx->sht.tw, ctx->sht.f, ctx->sht.H, ctx->sht.Q};
@@ -434,6 +435,17 @@ int qf_download_buffer(qf_ctx *ctx, int which, void *host)
         case QF_BUF_WHALF: src = ctx->Whalf; break;
         case QF_BUF_PHALF: src = ctx->Phalf; break;
         case QF_BUF_PW: src = ctx->PW; break;
+        case QF_BUF_MHD_P:
+        case QF_BUF_MHD_B:
+        case QF_BUF_MHD_ADVECTION:
+        case QF_BUF_MHD_LORENTZ:
+        case QF_BUF_MHD_INDUCTION:
+            if (!ctx->mhdb_mats) {
+                qf_set_error("qf_download_buffer: buffer %d is written by qf_mhd_spectral_budget, which has not run", which);
+                return QF_ERR_STATE;
+            }
+            src = ctx->mhdb_mats + (size_t)(which - QF_BUF_MHD_P) * ctx->N * ctx->N;
+            break;
         default:
             qf_set_error("qf_download_buffer: unknown buffer %d", which);
             return QF_ERR_INVALID;

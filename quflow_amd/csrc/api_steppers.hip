@@ -626,4 +626,77 @@ int qf_mhd_diagnostics(qf_ctx *ctx, double out[5])
     return QF_OK;
 }
 
+// out = (X Y - (X Y)^H) (1/hbar), the bracket [X, Y]/hbar of two skew-Hermitian matrices: the launches of the hydrodynamic
+// budget's tendency (budget_run, api_transforms.hip) in its order of operations; ctx->PW and ctx->Whalf are the scratch
+static int mhd_bracket(qf_ctx *ctx, const cplx *X, const cplx *Y, double inv_hb, cplx *out)
+{
+    QF_TRY(qf_launch_zgemm(ctx, X, Y, ctx->PW, nullptr));                                       // Z = X @ Y
+    QF_TRY(qf_launch_neg_conj_transpose(ctx, ctx->PW, ctx->Whalf));                             // -Z^H
+    QF_TRY(qf_launch_lincomb(ctx, 1.0, ctx->PW, 1.0, ctx->Whalf, 0.0, ctx->PW));                // Z - Z^H
+    QF_TRY(qf_launch_lincomb(ctx, inv_hb, ctx->PW, 0.0, (const cplx *)nullptr, 0.0, out));      // (Z - Z^H) (1/hbar)
+    return QF_OK;
+}
+
+// Where everything lives: W, Theta are the stack's members 0 and 1 (read only); P, B, [P,W]/hbar, [B,Theta]/hbar,
+// [P,Theta]/hbar in ctx->mhdb_mats; the packed diagonals and the sweep's results in the ten parts of ctx->mhdb_vec, the
+// coefficient arrays over the packed diagonals (dead after the sweep); the nine rows in ctx->mhdb_sums.
+int qf_mhd_spectral_budget(qf_ctx *ctx, int Nmax, double *out, double *coeffs)
+{
+    QF_TRY(check_ctx(ctx));
+    QF_TRY(need_stack(ctx, "qf_mhd_spectral_budget"));
+    const int N = ctx->N;
+    if (ctx->stack_k != 2) {
+        qf_set_error("qf_mhd_spectral_budget: the resident stack must be the pair (W, Theta) (k=%d)", ctx->stack_k);
+        return QF_ERR_INVALID;
+    }
+    if (!out) {
+        qf_set_error("qf_mhd_spectral_budget: null output");
+        return QF_ERR_INVALID;
+    }
+    if (Nmax <= 1 || Nmax > N) {
+        qf_set_error("qf_mhd_spectral_budget: band limit Nmax=%d outside 2..N=%d", Nmax, N);
+        return QF_ERR_INVALID;
+    }
+    QF_TRY(qf_refuse_forcing(ctx, "qf_mhd_spectral_budget"));
+    if (ctx->ham_table || ctx->ham_offset_on) {
+        qf_set_error("qf_mhd_spectral_budget: a Hamiltonian is installed on this context (qf_set_hamiltonian); the MHD "
+                     "budget is that of the built-in system P = Delta^-1 W, B = Delta Theta");
+        return QF_ERR_UNSUPPORTED;
+    }
+    if (ctx->slab_budget > 0) {       // (the slab plan's refusal comes before anything is launched)
+        std::vector<int> first;
+        long long need = 0;
+        QF_TRY(qf_slab_plan(N, Nmax, ctx->slab_budget, first, &need));
+    } else if (!ctx->basis) {
+        qf_set_error("qf_mhd_spectral_budget: no quantization basis on this context (qf_basis_compute, or qf_basis_stream)");
+        return QF_ERR_STATE;
+    }
+    const size_t NN = (size_t)N * N, half = (size_t)N * (N + 1) / 2, LL = (size_t)Nmax * Nmax;
+    if (!ctx->mhdb_sums) QF_HIP(hipMalloc((void **)&ctx->mhdb_sums, (size_t)9 * N * sizeof(double)));
+    if (!ctx->mhdb_vec) QF_HIP(hipMalloc((void **)&ctx->mhdb_vec, 10 * half * sizeof(cplx)));
+    if (!ctx->mhdb_mats) QF_HIP(hipMalloc((void **)&ctx->mhdb_mats, 5 * NN * sizeof(cplx)));
+    const cplx *W = ctx->stack[0], *Theta = ctx->stack[5];
+    cplx *P = ctx->mhdb_mats, *B = P + NN, *adv = P + 2 * NN, *lor = P + 3 * NN, *ind = P + 4 * NN;
+    const double inv_hb = 1.0 / qf_hbar(N);
+    QF_TRY(qf_launch_hamiltonian(ctx, W, P, 1.0));             // P = Delta^-1 W (nothing is installed: ctx->poisson)
+    QF_TRY(qf_launch_laplace(ctx, Theta, B));                  // B = Delta Theta
+    QF_TRY(mhd_bracket(ctx, P, W, inv_hb, adv));
+    QF_TRY(mhd_bracket(ctx, B, Theta, inv_hb, lor));
+    QF_TRY(mhd_bracket(ctx, P, Theta, inv_hb, ind));
+    const cplx *mats[5] = {W, Theta, adv, lor, ind};
+    cplx *d[5], *z[5];
+    double *omega[5];
+    for (int v = 0; v < 5; ++v) {
+        d[v] = ctx->mhdb_vec + (size_t)v * half;
+        z[v] = ctx->mhdb_vec + (size_t)(5 + v) * half;
+        omega[v] = reinterpret_cast<double *>(d[v]);
+    }
+    QF_TRY(qf_launch_mhd_degree_budget(ctx, Nmax, mats, d, z, omega, ctx->mhdb_sums));
+    QF_HIP(hipMemcpyAsync(out, ctx->mhdb_sums, (size_t)9 * Nmax * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    for (int v = 0; coeffs && v < 5; ++v)
+        QF_HIP(hipMemcpyAsync(coeffs + v * LL, omega[v], LL * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
 }  // extern "C"

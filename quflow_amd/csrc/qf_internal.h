@@ -413,6 +413,11 @@ struct qf_ctx {
     std::vector<cplx *> stack;
     int stack_k = 0;
     double *mhd_part = nullptr;  // k_mhd_sums: 5 x 1024 block partials, then the five sums (on demand)
+    // qf_mhd_spectral_budget's own buffers (first call, kept): P, B and the three tendencies (5 N^2 complex, readable through
+    // qf_download_buffer); the five packed diagonals and five sweep results (10 x N(N+1)/2 complex; the coefficient arrays
+    // overlay the packed diagonals once the sweep is over); the nine rows
+    cplx *mhdb_mats = nullptr, *mhdb_vec = nullptr;
+    double *mhdb_sums = nullptr;
     cplx *hook_host[3] = {nullptr, nullptr, nullptr};   // pinned staging of the hooked steppers (hooks.hip), on demand
     size_t hook_host_bytes = 0;
     cplx *ns_inv = nullptr;  // Newton-Schulz inverse of I - E (isomp_simple / isomp_quasinewton), on demand
@@ -686,6 +691,15 @@ int qf_launch_mat2shr(qf_ctx *ctx, int Nmax, const cplx *W_dev, double *omega_de
 // overlay the packed diagonals too (dead after the sweep).
 int qf_launch_degree_budget(qf_ctx *ctx, int Nmax, int nv, const cplx *const mats[3], cplx *const z[3], double *const omega[3],
                             double *sums_dev);
+// The MHD budget's transform stage: omega[v] = mat2shr(mats[v]) band-limited to Nmax for the five matrices W, Theta,
+// advection, Lorentz term, induction -- each with the bits of qf_launch_mat2shr alone -- then the nine rows of
+// include/quflow_hip.h (qf_mhd_spectral_budget) into sums_dev[r * Nmax + l].  ONE sweep of the basis (resident, or slab by
+// slab) carries all five vectors (k_block_vecmat_five).
+// d[v], z[v] (>= N(N+1)/2 complex each), omega[v] (>= Nmax^2 doubles each) and sums_dev (9 Nmax doubles) are the caller's:
+// d, z and the matrices are disjoint; omega[v] may overlay d[v] (dead after the sweep).  Nothing of the context is written
+// but the streamed form's slab.
+int qf_launch_mhd_degree_budget(qf_ctx *ctx, int Nmax, const cplx *const mats[5], cplx *const d[5], cplx *const z[5],
+                                double *const omega[5], double *sums_dev);
 int qf_launch_shc2mat(qf_ctx *ctx, const double *omega_dev, cplx *W_dev);
 int qf_launch_mat2shc(qf_ctx *ctx, const cplx *W_dev, double *omega_dev);
 

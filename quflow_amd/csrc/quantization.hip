@@ -22,7 +22,8 @@
 // its advective tendency, the forcing -- and pays ONE sweep for them: k_block_vecmat_multi carries all their packed
 // diagonals through the row loop k_block_vecmat runs (block_vecmat_rows, written once), so each entry of the basis is
 // read once and every coefficient column keeps the bits of mat2shr alone; k_degree_sums then reduces the products
-// omega_lm v_lm over m, one wavefront per degree.
+// omega_lm v_lm over m, one wavefront per degree.  The MHD budget (qf_mhd_spectral_budget) carries five matrices through
+// the same row loop (k_block_vecmat_five) and reduces nine pairs of columns (k_degree_pair_sums).
 #include "qf_internal.h"
 
 #pragma clang fp contract(off)   // the table of the direct Laplacian follows the reference's op order
@@ -346,13 +347,27 @@ struct vecmat_vectors {
 // The accumulation order of a vector depends on the row and column indices alone -- wave w takes the rows w, w + 4, ... of
 // every 256-row chunk in ascending order, then (wave 0 + wave 1) + (wave 2 + wave 3) -- never on NV or on the other
 // vectors, so every column has the bits it has when it is swept alone.
-template <int NV, bool SLAB>
+// FOLD: the waves' partial sums take the place of the staged diagonals once the row loop is over (one barrier more), which
+// halves the LDS of a workgroup -- the arithmetic and its order are the same.
+template <int NV, bool FOLD>
+struct vecmat_lds {
+    cplx ds[NV][256];
+    double part[4][NV][2][64];
+};
+template <int NV>
+struct vecmat_lds<NV, true> {
+    union {
+        cplx ds[NV][256];
+        double part[4][NV][2][64];
+    };
+};
+
+template <int NV, bool SLAB, bool FOLD = false>
 __device__ __forceinline__ void block_vecmat_rows(int N, int Nmax, int m0, const double *__restrict__ basis,
                                                   const vecmat_vectors<NV> &p, int m, int nload)
 {
     constexpr int KCH = 256;
-    __shared__ cplx ds[NV][KCH];
-    __shared__ double part[4][NV][2][64];
+    __shared__ vecmat_lds<NV, FOLD> lds;
     const int n = N - m;
     const int J = Nmax - m;
     const int j0 = blockIdx.x * 64;
@@ -374,7 +389,7 @@ __device__ __forceinline__ void block_vecmat_rows(int N, int Nmax, int m0, const
             for (int v = 0; v < NV; ++v) {
                 cplx a = make_double2(0.0, 0.0);
                 if (k < n && v < nload) a = p.d[v][dof + k];
-                ds[v][threadIdx.x] = a;
+                lds.ds[v][threadIdx.x] = a;
             }
         }
         __syncthreads();
@@ -393,7 +408,7 @@ __device__ __forceinline__ void block_vecmat_rows(int N, int Nmax, int m0, const
                 if (k < kend) {
 #pragma unroll
                     for (int v = 0; v < NV; ++v) {
-                        const cplx d = ds[v][k];
+                        const cplx d = lds.ds[v][k];
                         acc[v][0] += d.x * b[u];
                         acc[v][1] += d.y * b[u];
                     }
@@ -401,17 +416,18 @@ __device__ __forceinline__ void block_vecmat_rows(int N, int Nmax, int m0, const
             }
         }
     }
+    if (FOLD) __syncthreads();      // (every wave is done reading lds.ds before lds.part overwrites it)
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-        part[wave][v][0][lane] = acc[v][0];
-        part[wave][v][1][lane] = acc[v][1];
+        lds.part[wave][v][0][lane] = acc[v][0];
+        lds.part[wave][v][1][lane] = acc[v][1];
     }
     __syncthreads();
     if (wave == 0 && live) {
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-            const double re = (part[0][v][0][lane] + part[1][v][0][lane]) + (part[2][v][0][lane] + part[3][v][0][lane]);
-            const double im = (part[0][v][1][lane] + part[1][v][1][lane]) + (part[2][v][1][lane] + part[3][v][1][lane]);
+            const double re = (lds.part[0][v][0][lane] + lds.part[1][v][0][lane]) + (lds.part[2][v][0][lane] + lds.part[3][v][0][lane]);
+            const double im = (lds.part[0][v][1][lane] + lds.part[1][v][1][lane]) + (lds.part[2][v][1][lane] + lds.part[3][v][1][lane]);
             p.z[v][dof + j] = make_double2(re, im);
         }
     }
@@ -438,6 +454,16 @@ __global__ __launch_bounds__(256) void k_block_vecmat_multi(int N, int Nmax, int
                                                              vecmat_vectors<NV> p)
 {
     block_vecmat_rows<NV, SLAB>(N, Nmax, m0, basis, p, m0 + blockIdx.y, NV);
+}
+
+// ---- ... and for the five matrices of the MHD budget (W, Theta, advection, Lorentz term, induction), folded: 20 KB of LDS
+// per workgroup where the unfolded loop would take 40 KB.  Measured (N = 2048, kernel time): folded 5.66 ms,
+// unfolded 5.79 ms, two sweeps of three and two vectors 4.97 + 4.87 ms; mat2shr's one-vector sweep 4.70 ms.
+template <bool SLAB>
+__global__ __launch_bounds__(256) void k_block_vecmat_five(int N, int Nmax, int m0, const double *__restrict__ basis,
+                                                            vecmat_vectors<5> p)
+{
+    block_vecmat_rows<5, SLAB, true>(N, Nmax, m0, basis, p, m0 + blockIdx.y, 5);
 }
 
 // ---- m-major results z -> omega with the convention factors
@@ -484,6 +510,17 @@ struct degree_rows {
     const double *v[3];
     double scale[3];
 };
+// the sum of degree l over the 64 lanes of one wavefront, in every lane: written once for both kernels below
+__device__ __forceinline__ double degree_sum(const double *__restrict__ u, const double *__restrict__ v, int l, int lane)
+{
+    const size_t base = (size_t)l * l;
+    const int count = 2 * l + 1;
+    double s = 0.0;
+    for (int t = lane; t < count; t += 64) s += u[base + t] * v[base + t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    return s;
+}
 __global__ __launch_bounds__(256) void k_degree_sums(int Nmax, const double *__restrict__ u, degree_rows rows,
                                                       double *__restrict__ out)
 {
@@ -493,13 +530,27 @@ __global__ __launch_bounds__(256) void k_degree_sums(int Nmax, const double *__r
     const int r = blockIdx.y;
     const double *__restrict__ v = r == 0 ? rows.v[0] : (r == 1 ? rows.v[1] : rows.v[2]);
     const double sc = r == 0 ? rows.scale[0] : (r == 1 ? rows.scale[1] : rows.scale[2]);
-    const size_t base = (size_t)l * l;
-    const int count = 2 * l + 1;
-    double s = 0.0;
-    for (int t = lane; t < count; t += 64) s += u[base + t] * v[base + t];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    const double s = degree_sum(u, v, l, lane);
     if (lane == 0) out[(size_t)r * Nmax + l] = sc * s;
+}
+
+// ---- the pair form: out[r * Nmax + l] = scale_r sum_m u_r[l^2+l+m] v_r[l^2+l+m] for a table of (u, v, scale), one grid row
+// per pair (the nine rows of the MHD budget).  The table is a kernel argument: it is read from the argument segment at
+// blockIdx.y, never copied to private memory.
+constexpr int QF_DEGREE_PAIRS = 9;
+struct degree_pairs {
+    const double *u[QF_DEGREE_PAIRS];
+    const double *v[QF_DEGREE_PAIRS];
+    double scale[QF_DEGREE_PAIRS];
+};
+__global__ __launch_bounds__(256) void k_degree_pair_sums(int Nmax, degree_pairs pairs, double *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (l >= Nmax) return;                    // (whole wavefronts leave)
+    const int r = blockIdx.y;
+    const double s = degree_sum(pairs.u[r], pairs.v[r], l, lane);
+    if (lane == 0) out[(size_t)r * Nmax + l] = pairs.scale[r] * s;
 }
 
 // The streamed form's slabs for band limit Nmax, planned and the slab grown to the largest of them (hipFree waits for the
@@ -609,6 +660,20 @@ int vecmat_multi(qf_ctx *ctx, int nv, dim3 grid, int Nmax, int m0, const double 
     return QF_OK;
 }
 
+// the five vectors of the MHD budget over one slab or the resident basis
+template <bool SLAB>
+int vecmat_five(qf_ctx *ctx, dim3 grid, int Nmax, int m0, const double *basis, cplx *const d[5], cplx *const z[5])
+{
+    vecmat_vectors<5> p;
+    for (int v = 0; v < 5; ++v) {
+        p.d[v] = d[v];
+        p.z[v] = z[v];
+    }
+    hipLaunchKernelGGL((k_block_vecmat_five<SLAB>), grid, dim3(256), 0, ctx->stream, ctx->N, Nmax, m0, basis, p);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
 }  // namespace
 
 // mat2shr of nv matrices in ONE sweep of the basis, then the per-degree sums of omega_0 * omega_r.  The diagonals are
@@ -647,6 +712,46 @@ int qf_launch_degree_budget(qf_ctx *ctx, int Nmax, int nv, const cplx *const mat
         QF_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_degree_sums, dim3((Nmax + 3) / 4, nv), dim3(256), 0, ctx->stream, Nmax, omega[0], rows, sums_dev);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+// The MHD budget's transform stage (qf_api.h): as qf_launch_degree_budget, for five matrices and nine rows.
+int qf_launch_mhd_degree_budget(qf_ctx *ctx, int Nmax, const cplx *const mats[5], cplx *const d[5], cplx *const z[5],
+                                double *const omega[5], double *sums_dev)
+{
+    const int N = ctx->N;
+    std::vector<int> first;
+    if (ctx->slab_budget > 0) QF_TRY(reserve_slabs(ctx, Nmax, first));
+    dim3 gp((N + 255) / 256, Nmax);
+    for (int v = 0; v < 5; ++v) {
+        hipLaunchKernelGGL(k_pack_diags<MODE_SHR>, gp, dim3(256), 0, ctx->stream, N, Nmax, mats[v], d[v], (cplx *)nullptr);
+        QF_HIP(hipGetLastError());
+    }
+    if (ctx->slab_budget == 0) {
+        QF_TRY(vecmat_five<false>(ctx, dim3((Nmax + 63) / 64, Nmax), Nmax, 0, ctx->basis, d, z));
+    } else {
+        for (size_t s = 0; s + 1 < first.size(); ++s) {
+            const int m0 = first[s], m1 = first[s + 1];
+            QF_TRY(generate_slab(ctx, Nmax, m0, m1));
+            QF_TRY(vecmat_five<true>(ctx, dim3((Nmax - m0 + 63) / 64, m1 - m0), Nmax, m0, ctx->slab, d, z));
+        }
+    }
+    dim3 gu((Nmax + 255) / 256, Nmax);
+    for (int v = 0; v < 5; ++v) {
+        hipLaunchKernelGGL(k_unpack_coeffs<MODE_SHR>, gu, dim3(256), 0, ctx->stream, N, Nmax, z[v], (const cplx *)nullptr, omega[v]);
+        QF_HIP(hipGetLastError());
+    }
+    // rows 0..8: ww, tt, wt, 2 wa, 2 wb, 2 tc, ta, tb, wc   (0 omega, 1 theta, 2 advection, 3 Lorentz, 4 induction)
+    static const int iu[QF_DEGREE_PAIRS] = {0, 1, 0, 0, 0, 1, 1, 1, 0};
+    static const int iv[QF_DEGREE_PAIRS] = {0, 1, 1, 2, 3, 4, 2, 3, 4};
+    degree_pairs pairs;
+    for (int r = 0; r < QF_DEGREE_PAIRS; ++r) {
+        pairs.u[r] = omega[iu[r]];
+        pairs.v[r] = omega[iv[r]];
+        pairs.scale[r] = (r >= 3 && r <= 5) ? 2.0 : 1.0;
+    }
+    hipLaunchKernelGGL(k_degree_pair_sums, dim3((Nmax + 3) / 4, QF_DEGREE_PAIRS), dim3(256), 0, ctx->stream, Nmax, pairs, sums_dev);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }

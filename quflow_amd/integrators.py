@@ -1366,6 +1366,20 @@ class DeviceStackTrajectory:
         """DeviceTrajectory.spectral_budget of member j (the built-in Hamiltonian, no forcing)."""
         return self._select(j).spectral_budget(lmax, coefficients)
 
+    def mhd_budget(self, lmax=None, coefficients=False):
+        """quflow_amd.analysis.mhd_spectral_budget of the resident pair (W, Theta) -- spectra of the kinetic and magnetic
+        energy, the mean-square potential and the cross helicity, their transfers and fluxes per degree -- from one sweep of
+        the basis; 9 lmax doubles cross PCIe (and the coefficients when asked).  The stack and the statistics of the run are
+        untouched: the next `advance` continues bit for bit as if the call had not happened.  `spectral_budget(j)` remains
+        the hydrodynamic budget of one member taken alone."""
+        from . import analysis
+        if not self.magnetic or self.k != 2:
+            raise ValueError("mhd_budget is the budget of the MHD pair (W, Theta): this stack is not magnetic (k=%d)" % self.k)
+        nmax = analysis._band_limit(self.N, lmax)
+        analysis._check_budget_mode("mhd_budget")
+        self._member._need_basis()
+        return analysis._mhd_budget_call(self.ctx, nmax, coefficients)
+
     def spectrum(self, j):
         """DeviceTrajectory.spectrum of member j: the invariant of the flow for every member of the stack."""
         return self._select(j).spectrum()
