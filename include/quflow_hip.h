@@ -489,6 +489,27 @@ int qf_degree_spectrum(qf_ctx *ctx, const void *W_host, int Nmax, double *Z);
 int qf_shr2fun(qf_ctx *ctx, const double *omega_host, long long n_omega, int L, int berezin, double *f_host);
 /* omega: n_omega complex128; isreal: f_host is double (L, 2L-1) (the m >= 0 half of omega, a real map), else complex128 */
 int qf_shc2fun(qf_ctx *ctx, const void *omega_host, long long n_omega, int L, int berezin, int isreal, void *f_host);
+/* Function-space output of a state (the reference's 'fun', 'funL2', 'funhalf', 'funL2half' rows, quflow/simulation.py:
+ * 287-344): nfields real grids of W (NULL: the resident state ctx->W -- for a resident stack the member qf_states_select
+ * chose; else an N x N complex128 matrix, uploaded to the staging matrix as qf_mat2shr does).  Field i is
+ *     qf_shr2fun(mat2shr(W)[:n_omega], L, berezin)   with L = sqrt(n_omega) (n_omega no square: the next integer above;
+ *                                                    the last degree, cut short, stays zero as in qf_shr2fun),
+ * bit for bit, written to f_host[i] as (L, 2L-1), row-major, doubles (dtype 0) or floats (dtype 1: each double converted
+ * with round-to-nearest-even on the device, what numpy's astype does).  The state goes through mat2shr ONCE, band-limited to
+ * the largest L asked for (with a streamed basis: once per bandwidth); the fields of one bandwidth share ONE synthesis --
+ * one walk of the Legendre recurrence and one gather of the twiddles for all of them.
+ * Needs the transforms' mode set as qf_mat2shr does.  Only the transforms' staging, ctx->sht and the device copy of the
+ * coefficients (which then holds mat2shr of the state, band-limited to the largest L) are written: the state, the carried
+ * increment, the statistics and what is installed stay, and a resident run continues bit for bit as if the call had not
+ * happened.  QF_ERR_INVALID, before anything is launched and with the field named: nfields outside 1..8 or more than 4
+ * fields of one bandwidth, a null pointer, a dtype other than 0 / 1, n_omega < 1, L > ctx->N or L > 8192; QF_ERR_STATE for W_host == NULL
+ * on a context that holds a complex64 state only, and without a basis in resident mode. */
+typedef struct { long long n_omega; int berezin; int dtype; } qf_field;   /* dtype: 0 = float64, 1 = float32 */
+int qf_state_fields(qf_ctx *ctx, const void *W_host, int nfields, const qf_field *fields, void *const *f_host);
+/* The first n_omega real coefficients of the device copy (what the last qf_mat2shr, qf_state_fields, qf_shr2mat or
+ * qf_fun2shr(NULL) left there), copied out without another sweep: after qf_state_fields with a field of bandwidth N they are
+ * qf_mat2shr of the same state, bit for bit.  QF_ERR_STATE when the copy holds fewer than n_omega real coefficients. */
+int qf_shr_held(qf_ctx *ctx, double *omega_host, long long n_omega);
 /* fun2shc / fun2shr (quflow/transforms.py:189-217, 404-419): McEwen-Wiaux analysis of the MW grid f (L, 2L-1), row-major,
  * double when isreal != 0, else complex128; 1 <= L <= 8192, independent of ctx->N, no quantization basis needed.
  * qf_fun2shc writes L^2 complex128 (index l^2 + l + m), qf_fun2shr the L^2 doubles shc2shr makes of them.  The inverse of

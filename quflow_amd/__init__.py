@@ -30,7 +30,7 @@ QuSimulation = Simulation          # the reference's name (quflow/simulation.py:
 from .quantization import (shr2mat, mat2shr, shc2mat, mat2shc, get_basis, compute_basis, basis_break_index, elm2ind, ind2elm,
                            berezin_multipliers, elmr2mat, elmc2mat)
 from .transforms import (shr2fun, shc2fun, shr2shc, shc2shr, as_fun, as_shr, sphgrid, fun2img, img2fun, fun2shr,
-                         fun2shc)
+                         fun2shc, state_fields)
 from .geometry import hbar, bracket, norm_L2, inner_L2, norm_Linf, norm_L1, integral, qtime2seconds, seconds2qtime
 from .geometry import so3_generators, cartesian_generators, rotate, rotation_matrix, grad
 from .dynamics import blob, north_blob, project_el

@@ -70,6 +70,13 @@ class EighStats(ctypes.Structure):
                 ("off", ctypes.c_double)]
 
 
+class Field(ctypes.Structure):
+    """qf_field: one function-space output of qf_state_fields (dtype: 0 = float64, 1 = float32)."""
+    _fields_ = [("n_omega", ctypes.c_longlong),
+                ("berezin", ctypes.c_int),
+                ("dtype", ctypes.c_int)]
+
+
 # every symbol include/quflow_hip.h declares: (restype, argtypes)
 _vp = ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -161,6 +168,8 @@ SIGNATURES = {
     "qf_degree_spectrum": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp]),
     "qf_shr2fun": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_shc2fun": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "qf_state_fields": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.POINTER(Field), ctypes.POINTER(_vp)]),
+    "qf_shr_held": (ctypes.c_int, [_vp, _vp, ctypes.c_longlong]),
     "qf_fun2shc": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_fun2shr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_diagnostics": (ctypes.c_int, [_vp, _dp, _dp]),

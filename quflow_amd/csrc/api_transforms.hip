@@ -331,11 +331,18 @@ static int sht_args(const char *who, long long n_omega, int L, const void *f_hos
 }
 
 // ctx->sht grown to what (L, isreal) needs; a buffer that is too small is replaced (hipFree waits for the device)
+static int sht_reserve_bytes(qf_ctx *ctx, const size_t want[8]);
+
 static int sht_reserve(qf_ctx *ctx, int L, int isreal, bool analysis = false)
 {
     size_t want[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (analysis) qf_sht_analysis_sizes(L, isreal, want);
     else qf_sht_sizes(L, isreal, want);
+    return sht_reserve_bytes(ctx, want);
+}
+
+static int sht_reserve_bytes(qf_ctx *ctx, const size_t want[8])
+{
     qf_sht &S = ctx->sht;
     void **bufs[8] = {(void **)&S.omega, (void **)&S.tab, (void **)&S.col, (void **)&S.At, (void **)&S.tw, (void **)&S.f,
                       (void **)&S.H, (void **)&S.Q};
@@ -355,22 +362,33 @@ static int sht_reserve(qf_ctx *ctx, int L, int isreal, bool analysis = false)
 //   tab[l]     = sqrt(4 pi) w_l,  w_l^2 = prod_{j=1..l} (L-j)/(L+j) -- berezin_multipliers(L) (utils.py:108-135, whose
 //                lgamma form is this product), or 1 without Berezin;
 //   tab[L + m] = lambda_mm(theta) / sin^m(theta) = (-1)^m sqrt((2m+1)/(4 pi) prod_{k=1..m} (2k-1)/(2k)).
-static int sht_tables(qf_ctx *ctx, int L, int berezin)
+static void sht_multiplier_row(int L, int berezin, double *row)
 {
-    std::vector<double> tab(2 * (size_t)L);
     const long double fourpi = 4.0L * 3.141592653589793238462643383279502884L;
     const long double rt4pi = std::sqrt(fourpi);
     long double q = 1.0L;
     for (int l = 0; l < L; ++l) {
         if (l > 0) q *= (long double)(L - l) / (long double)(L + l);
-        tab[l] = (double)(berezin ? rt4pi * std::sqrt(q) : rt4pi);
+        row[l] = (double)(berezin ? rt4pi * std::sqrt(q) : rt4pi);
     }
+}
+
+static void sht_seed_row(int L, double *row)
+{
+    const long double fourpi = 4.0L * 3.141592653589793238462643383279502884L;
     long double prod = 1.0L;
     for (int m = 0; m < L; ++m) {
         if (m > 0) prod *= (long double)(2 * m - 1) / (long double)(2 * m);
         const double v = (double)std::sqrt((long double)(2 * m + 1) / fourpi * prod);
-        tab[(size_t)L + m] = (m & 1) ? -v : v;
+        row[m] = (m & 1) ? -v : v;
     }
+}
+
+static int sht_tables(qf_ctx *ctx, int L, int berezin)
+{
+    std::vector<double> tab(2 * (size_t)L);
+    sht_multiplier_row(L, berezin, tab.data());
+    sht_seed_row(L, tab.data() + L);
     QF_HIP(hipMemcpyAsync(ctx->sht.tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     QF_HIP(hipStreamSynchronize(ctx->stream));     // (tab is gone at return)
     return QF_OK;
@@ -424,6 +442,157 @@ int qf_shc2fun(qf_ctx *ctx, const void *omega_host, long long n_omega, int L, in
     }
     const long long n = std::min(n_omega, (long long)L * L);
     return sht_run(ctx, omega_host, nullptr, n, L, berezin, 0, isreal ? 1 : 0, f_host);
+}
+
+// ---- function-space output of a state (include/quflow_hip.h): mat2shr once, one stacked synthesis per bandwidth
+int qf_state_fields(qf_ctx *ctx, const void *W_host, int nfields, const qf_field *fields, void *const *f_host)
+{
+    QF_TRY(check_ctx(ctx));
+    const char *who = "qf_state_fields";
+    constexpr int MAXF = 8, MAXG = 4;
+    if (nfields < 1 || nfields > MAXF) {
+        qf_set_error("%s: %d fields (1..%d in all, at most %d of one bandwidth)", who, nfields, MAXF, MAXG);
+        return QF_ERR_INVALID;
+    }
+    if (!fields || !f_host) {
+        qf_set_error("%s: null field list", who);
+        return QF_ERR_INVALID;
+    }
+    // the groups: fields of one bandwidth, in the order of their first member
+    struct group {
+        int L, nf, idx[MAXG];
+    } groups[MAXF];
+    int ngroups = 0, Lmax = 0;
+    long long nvalid[MAXF];
+    for (int i = 0; i < nfields; ++i) {
+        const qf_field &fd = fields[i];
+        if (fd.n_omega < 1) {
+            qf_set_error("%s: field %d: empty coefficient array (n_omega=%lld)", who, i, fd.n_omega);
+            return QF_ERR_INVALID;
+        }
+        if (fd.dtype != 0 && fd.dtype != 1) {
+            qf_set_error("%s: field %d: dtype %d (0 = float64, 1 = float32)", who, i, fd.dtype);
+            return QF_ERR_INVALID;
+        }
+        if (!f_host[i]) {
+            qf_set_error("%s: field %d: null output grid", who, i);
+            return QF_ERR_INVALID;
+        }
+        // whole degrees only, as qf_shr2fun: E^2 the largest square <= n_omega enters, the bandwidth is E, or E + 1 when
+        // n_omega is no square (the last degree, cut short, stays zero)
+        long long e = (long long)std::sqrt((double)fd.n_omega);
+        while (e * e > fd.n_omega) --e;
+        while ((e + 1) * (e + 1) <= fd.n_omega) ++e;
+        const long long L = e * e == fd.n_omega ? e : e + 1;
+        if (L > ctx->N || L > 8192) {      // (8192: the synthesis kernels' limit, as in sht_args)
+            qf_set_error("%s: field %d: bandwidth L=%lld of n_omega=%lld exceeds %s", who, i, L, fd.n_omega,
+                         L > ctx->N ? "the context's N" : "8192");
+            return QF_ERR_INVALID;
+        }
+        nvalid[i] = e * e;
+        int g = 0;
+        while (g < ngroups && groups[g].L != (int)L) ++g;
+        if (g == ngroups) {
+            groups[ngroups].L = (int)L;
+            groups[ngroups].nf = 0;
+            ++ngroups;
+        }
+        if (groups[g].nf == MAXG) {
+            qf_set_error("%s: field %d: more than %d fields of bandwidth L=%lld", who, i, MAXG, L);
+            return QF_ERR_INVALID;
+        }
+        groups[g].idx[groups[g].nf++] = i;
+        Lmax = std::max(Lmax, (int)L);
+    }
+    if (!W_host && ctx->c64 && !ctx->w_c128_set) {
+        qf_set_error("%s: this context holds a complex64 state only; the fields are double precision (pass W_host)", who);
+        return QF_ERR_STATE;
+    }
+    // Resident basis: a column of the sweep is summed over its rows in an order that does not depend on the band limit, so
+    // the leading L^2 coefficients of the sweep to Lmax are those of the sweep to L, bit for bit: one sweep serves every
+    // bandwidth.  Streamed basis: the blocks are generated per band limit; one sweep per bandwidth, as qf_mat2shr does.
+    const bool one_sweep = ctx->slab_budget == 0;
+    if (!one_sweep)
+        for (int g = 0; g < ngroups; ++g) {       // (the slab plan's refusal comes before anything is launched)
+            std::vector<int> first;
+            long long need = 0;
+            QF_TRY(qf_slab_plan(ctx->N, groups[g].L, ctx->slab_budget, first, &need));
+        }
+    QF_TRY(need_source(ctx, who));
+    size_t want[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int g = 0; g < ngroups; ++g) {
+        size_t b[6];
+        qf_sht_fields_sizes(groups[g].L, groups[g].nf, b);
+        for (int i = 0; i < 6; ++i) want[i] = std::max(want[i], b[i]);
+    }
+    want[0] = 0;      // (the coefficients stay in ctx->sh_omega)
+    QF_TRY(sht_reserve_bytes(ctx, want));
+    const size_t NN = (size_t)ctx->N * ctx->N;
+    const cplx *src = ctx->W;
+    if (W_host) {
+        QF_HIP(hipMemcpyAsync(ctx->stage, W_host, NN * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
+        src = ctx->stage;
+    }
+    ctx->sh_shr_count = 0;
+    // the host tables are the pageable sources of asynchronous copies: they live until the stream is synchronised, which
+    // happens below on the error path too
+    std::vector<double> tabs[MAXF];
+    auto enqueue = [&]() -> int {
+    for (int g = 0; g < ngroups; ++g) {
+        const int L = groups[g].L, nf = groups[g].nf;
+        if (g == 0 || !one_sweep) {
+            const int Ls = one_sweep ? Lmax : L;
+            ctx->sh_shr_count = 0;
+            QF_HIP(hipMemsetAsync(ctx->sh_omega, 0, (size_t)Ls * Ls * sizeof(double), ctx->stream));
+            QF_TRY(qf_launch_mat2shr(ctx, Ls, src, ctx->sh_omega));
+            ctx->sh_shr_count = (long long)Ls * Ls;
+        }
+        std::vector<double> &tab = tabs[g];
+        tab.resize(((size_t)nf + 1) * L);
+        long long n[MAXG] = {0, 0, 0, 0};
+        unsigned f32mask = 0;
+        for (int f = 0; f < nf; ++f) {
+            const qf_field &fd = fields[groups[g].idx[f]];
+            sht_multiplier_row(L, fd.berezin, tab.data() + (size_t)f * L);
+            n[f] = nvalid[groups[g].idx[f]];
+            if (fd.dtype == 1) f32mask |= 1u << f;
+        }
+        sht_seed_row(L, tab.data() + (size_t)nf * L);
+        QF_HIP(hipMemcpyAsync(ctx->sht.tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        QF_TRY(qf_launch_sht_fields(ctx, L, nf, n, f32mask, ctx->sh_omega));
+        const size_t slot = (size_t)L * (2 * (size_t)L - 1);
+        for (int f = 0; f < nf; ++f) {
+            const int i = groups[g].idx[f];
+            QF_HIP(hipMemcpyAsync(f_host[i], ctx->sht.f + (size_t)f * slot, slot * (fields[i].dtype == 1 ? sizeof(float) : sizeof(double)),
+                                  hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    return QF_OK;
+    };
+    const int rc = enqueue();
+    if (rc != QF_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
+}
+
+int qf_shr_held(qf_ctx *ctx, double *omega_host, long long n_omega)
+{
+    QF_TRY(check_ctx(ctx));
+    if (!omega_host || n_omega < 1) {
+        qf_set_error("qf_shr_held: null or empty output (n_omega=%lld)", n_omega);
+        return QF_ERR_INVALID;
+    }
+    if (!ctx->sh_omega || ctx->sh_shr_count < n_omega) {
+        qf_set_error("qf_shr_held: the device copy holds %lld real coefficients, %lld were asked for", ctx->sh_omega ? ctx->sh_shr_count : 0LL,
+                     n_omega);
+        return QF_ERR_STATE;
+    }
+    QF_HIP(hipMemcpyAsync(omega_host, ctx->sh_omega, (size_t)n_omega * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    QF_HIP(hipStreamSynchronize(ctx->stream));
+    return QF_OK;
 }
 
 // ---- spherical-harmonic analysis (quflow/transforms.py:189-217, 404-419; kernels in sht.hip) ------------------

@@ -317,7 +317,8 @@ struct qf_event_pair {
 // buffer has.
 struct qf_sht {
     double *omega = nullptr;     // coefficients uploaded from the host (min(n_omega, L^2) entries, real or complex)
-    double *tab = nullptr;       // 2 L doubles: sqrt(4 pi) w_l, then the seeds lambda_mm / sin^m (host-made, long double)
+    double *tab = nullptr;       // 2 L doubles: sqrt(4 pi) w_l, then the seeds lambda_mm / sin^m (host-made, long double);
+                                 // the stacked synthesis keeps one row of multipliers per field before the seeds
     cplx *col = nullptr;         // 2 x L(L+1)/2 complex: a_lm and (-1)^m a_l,-m as m-major columns (l contiguous)
     double *At = nullptr;        // Kpad x ldA doubles: the Legendre stage's output, [k = 2m + (re, im)][ring]
     double2 *tw = nullptr;       // 2L - 1 twiddles (cos, sin)(2 pi k / (2L - 1))
@@ -708,6 +709,12 @@ int qf_launch_mat2shc(qf_ctx *ctx, const cplx *W_dev, double *omega_dev);
 // filled; result in ctx->sht.f: (L, 2L-1) doubles when isreal, complex128 otherwise.
 int qf_launch_sht_synth(qf_ctx *ctx, int L, int shr, int isreal, const double *omega_dev, long long n_valid);
 void qf_sht_sizes(int L, int isreal, size_t bytes[6]);   // what each ctx->sht buffer needs for (L, isreal)
+// stacked real synthesis (qf_state_fields): nf <= 4 real fields of bandwidth L from the one real vector omega_dev, field f
+// keeping the coefficients below n_valid[f].  ctx->sht.tab holds nf rows of L multipliers, then the L seeds.  Field f lands
+// in slot f of ctx->sht.f (slots of L (2L-1) doubles): doubles, or floats packed at the slot's start where bit f of f32mask
+// is set.  Each field has the bits of qf_launch_sht_synth(shr = 1, isreal = 1) of the same coefficients.
+int qf_launch_sht_fields(qf_ctx *ctx, int L, int nf, const long long *n_valid, unsigned f32mask, const double *omega_dev);
+void qf_sht_fields_sizes(int L, int nf, size_t bytes[6]);   // what each ctx->sht buffer needs for nf fields of bandwidth L
 // analysis: the grid in ctx->sht.f (uploaded by the caller) -> L^2 coefficients in omega_dev, real (shr != 0: fun2shr) or
 // complex (fun2shc); needs ctx->sht.tab filled and ctx->sht.Q built for this L (qf_launch_sht_qbuild, which uses f and H
 // as its workspace: build before the grid is uploaded).

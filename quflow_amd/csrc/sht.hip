@@ -318,6 +318,189 @@ void sht_shape(int L, int isreal, int *M, int *K, int *ldA)
     *ldA = round_up(*M, SHT_BM);
 }
 
+// =====================================================================================================================
+// STACKED REAL SYNTHESIS (qf_state_fields): F <= 4 real fields of one bandwidth L from ONE real coefficient vector -- the
+// reference's 'fun' / 'funL2' / 'funhalf' / 'funL2half' outputs differ by the per-degree multiplier w_l and by how many
+// leading coefficients they keep, nothing else.  The recurrence lambda_lm(theta_t) is walked once per (ring, m) for all F
+// fields and the Fourier stage gathers each twiddle tile once for M = F L rows.  Every field is formed by the operations of
+// k_sht_pack<true, false>, k_sht_legendre<false> and k_sht_fourier in their order (the statements below are those kernels'
+// statements, repeated per field; a row of the Fourier stage meets the same K-steps whatever its row index), so a field
+// has the bits of qf_shr2fun of the same coefficients.  Layout: scale [F][L], col [F][L(L+1)/2], At [K][ldA] with field f
+// in the columns f L .. f L + L - 1 (ldA = round_up(F L, 64)), the grids in F slots of L (2L-1) doubles each.
+// =====================================================================================================================
+struct sht_field_lengths {
+    long long n[4];            // field f keeps the coefficients below n[f]; the rest count as zero
+};
+
+template <int F>
+__global__ __launch_bounds__(256) void k_sht_pack_fields(int L, sht_field_lengths len, const double *__restrict__ omega,
+                                                         const double *__restrict__ scale, cplx *__restrict__ col)
+{
+    const int m = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= L - m) return;
+    const long long l = m + j;
+    const long long ip = l * l + l + m, im = l * l + l - m;
+    const size_t o = col_offset(m, L) + j, half = (size_t)L * (L + 1) / 2;
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const long long n = len.n[f];
+        const double s = scale[(size_t)f * L + l];
+        cplx a;
+        const double xp = ip < n ? omega[ip] : 0.0;
+        if (m == 0) {
+            a = make_double2(xp, 0.0);
+        } else {
+            const double xm = im < n ? omega[im] : 0.0;
+            const double c = (1.0 / sqrt(2.0)) * ((m & 1) ? -1.0 : 1.0);
+            a = make_double2(c * xp, c * xm);
+        }
+        col[f * half + o] = make_double2(a.x * s, a.y * s);
+    }
+}
+
+template <int F>
+__global__ __launch_bounds__(SHT_RINGS) void k_sht_legendre_fields(int L, const double *__restrict__ seed,
+                                                                   const cplx *__restrict__ col, double *__restrict__ At, int ldA)
+{
+    __shared__ double2 rec[SHT_CHUNK];
+    __shared__ cplx cp[F][SHT_CHUNK];
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x * SHT_RINGS + tid;
+    const bool ring = t < L;
+    const int tt = ring ? t : L - 1;          // lanes past the last ring compute a copy of it and store nothing
+    const sht_ring g = sht_ring_of(tt, L);
+    const double x = g.x;
+    const int y = blockIdx.y;
+    const size_t half = (size_t)L * (L + 1) / 2;
+    for (int hf = 0; hf < 2; ++hf) {
+        const int m = hf == 0 ? y : L - 1 - y;
+        if (hf == 1 && m <= y) break;
+        int k;
+        double p1, p2 = 0.0;
+        sht_seed(m, seed[m], g, p1, k);
+        double fac = sht_factor(k);
+        // the sums are k_sht_legendre<false>'s `g += c * v`, which the compiler contracts to one fused multiply-add: written
+        // as fma() here, so that a field keeps those bits whatever a compiler decides about contraction in this kernel
+        double gr[F], gi[F];
+#pragma unroll
+        for (int f = 0; f < F; ++f) gr[f] = gi[f] = 0.0;
+        const cplx *cpm = col + col_offset(m, L);
+        for (int l0 = m; l0 < L; l0 += SHT_CHUNK) {
+            const int n = min(SHT_CHUNK, L - l0);
+            __syncthreads();
+            if (tid < n) {
+                const int l = l0 + tid;
+                rec[tid] = sht_ab(l, m);
+#pragma unroll
+                for (int f = 0; f < F; ++f) cp[f][tid] = cpm[f * half + (l - m)];
+            }
+            __syncthreads();
+            int i0 = 0;
+            if (l0 == m) {            // degree m: the seed itself
+                const double v = p1 * fac;
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    gr[f] = fma(cp[f][0].x, v, gr[f]);
+                    gi[f] = fma(cp[f][0].y, v, gi[f]);
+                }
+                i0 = 1;
+            }
+            for (int i = i0; i < n; ++i) {
+                const double v = sht_step(rec[i], x, p1, p2, k, fac);
+#pragma unroll
+                for (int f = 0; f < F; ++f) {
+                    const cplx c = cp[f][i];
+                    gr[f] = fma(c.x, v, gr[f]);
+                    gi[f] = fma(c.y, v, gi[f]);
+                }
+            }
+        }
+        if (ring) {
+            double *c0 = At + (size_t)(2 * m) * ldA, *c1 = c0 + ldA;
+            const double w = m == 0 ? 1.0 : 2.0;
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                c0[(size_t)f * L + t] = w * gr[f];
+                c1[(size_t)f * L + t] = m == 0 ? 0.0 : w * gi[f];
+            }
+        }
+    }
+}
+
+// The Fourier stage over M = F L stacked rows: k_sht_fourier's K-loop, statement for statement; the epilogue sends row r
+// to field r / L, ring r % L (a 64-row tile may span two fields), as a double or, where bit r / L of f32mask is set, as a
+// float by a plain conversion (round to nearest even: numpy's astype), packed at the start of the field's slot.
+__global__ __launch_bounds__(256) void k_sht_fourier_fields(int L, int M, int K, const double *__restrict__ At, int ldA,
+                                                            const double2 *__restrict__ tw, double *__restrict__ f,
+                                                            unsigned f32mask)
+{
+    __shared__ double As[SHT_BK][SHT_BM];
+    __shared__ double Bs[SHT_BK][SHT_BN];
+    const unsigned P = 2u * L - 1u;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int r16 = lane & 15, q4 = lane >> 4;
+    const int row0 = blockIdx.y * SHT_BM, col0 = blockIdx.x * SHT_BN;
+    qf_d4 acc[2][2];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = qf_d4{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < K; k0 += SHT_BK) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int idx = tid + 256 * r, kk = idx >> 6, c = idx & 63;
+            As[kk][c] = At[(size_t)(k0 + kk) * ldA + row0 + c];
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int idx = tid + 256 * r, mm = idx >> 6, c = idx & 63;
+            const unsigned m = (unsigned)(k0 >> 1) + mm, p = (unsigned)(col0 + c);
+            double cs = 0.0, sn = 0.0;
+            if (m < (unsigned)L && p < P) {
+                const double2 w = tw[(m * p) % P];
+                cs = w.x;
+                sn = -w.y;
+            }
+            Bs[2 * mm][c] = cs;
+            Bs[2 * mm + 1][c] = sn;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < SHT_BK / 4; ++s) {
+            double a[2], b[2];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) a[mi] = As[4 * s + q4][wm * 32 + mi * 16 + r16];
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) b[ni] = Bs[4 * s + q4][wn * 32 + ni * 16 + r16];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    const size_t slot = (size_t)L * P;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int row = row0 + wm * 32 + mi * 16 + q4 + 4 * reg;
+                const unsigned col = (unsigned)(col0 + wn * 32 + ni * 16 + r16);
+                if (row >= M || col >= P) continue;
+                const int fi = row / L, t = row - fi * L;
+                const double v = acc[mi][ni][reg];
+                double *slot_f = f + (size_t)fi * slot;
+                const size_t e = (size_t)t * P + col;
+                if ((f32mask >> fi) & 1u) reinterpret_cast<float *>(slot_f)[e] = (float)v;
+                else slot_f[e] = v;
+            }
+}
+
 
 // =====================================================================================================================
 // ANALYSIS (fun2shc / fun2shr): McEwen-Wiaux analysis on the same grid, the synthesis run backwards.  With P = 2L-1,
@@ -693,6 +876,59 @@ int qf_launch_sht_synth(qf_ctx *ctx, int L, int shr, int isreal, const double *o
     QF_HIP(hipGetLastError());
     const dim3 gf((P + SHT_BN - 1) / SHT_BN, ldA / SHT_BM);
     hipLaunchKernelGGL(k_sht_fourier, gf, dim3(256), 0, ctx->stream, L, M, K, S.At, ldA, S.tw, S.f, isreal ? 0 : 1);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+// ---- stacked real synthesis: what each ctx->sht buffer needs for nf fields of bandwidth L (tab: nf scale rows, then the seeds)
+void qf_sht_fields_sizes(int L, int nf, size_t bytes[6])
+{
+    const size_t LL = (size_t)L * L, P = 2 * (size_t)L - 1, half = (size_t)L * (L + 1) / 2;
+    bytes[0] = LL * sizeof(double);
+    bytes[1] = ((size_t)nf + 1) * L * sizeof(double);
+    bytes[2] = (size_t)nf * half * sizeof(cplx);
+    bytes[3] = (size_t)round_up(2 * L, SHT_BK) * round_up(nf * L, SHT_BM) * sizeof(double);
+    bytes[4] = P * sizeof(double2);
+    bytes[5] = (size_t)nf * L * P * sizeof(double);
+}
+
+namespace {
+
+template <int F>
+int launch_fields(qf_ctx *ctx, int L, const sht_field_lengths &len, const double *omega_dev, int ldA)
+{
+    qf_sht &S = ctx->sht;
+    const dim3 gp((L + 255) / 256, L), gl((L + SHT_RINGS - 1) / SHT_RINGS, (L + 1) / 2);
+    hipLaunchKernelGGL(k_sht_pack_fields<F>, gp, dim3(256), 0, ctx->stream, L, len, omega_dev, S.tab, S.col);
+    QF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_sht_legendre_fields<F>, gl, dim3(SHT_RINGS), 0, ctx->stream, L, S.tab + (size_t)F * L, S.col, S.At, ldA);
+    QF_HIP(hipGetLastError());
+    return QF_OK;
+}
+
+}  // namespace
+
+// nf real fields of bandwidth L from omega_dev into the nf slots of ctx->sht.f (slot f: L (2L-1) doubles, or as many floats
+// packed at its start where bit f of f32mask is set).  ctx->sht.tab holds nf scale rows and the seeds.
+int qf_launch_sht_fields(qf_ctx *ctx, int L, int nf, const long long *n_valid, unsigned f32mask, const double *omega_dev)
+{
+    qf_sht &S = ctx->sht;
+    const int P = 2 * L - 1, M = nf * L, K = round_up(2 * L, SHT_BK), ldA = round_up(M, SHT_BM);
+    sht_field_lengths len = {{0, 0, 0, 0}};
+    for (int f = 0; f < nf; ++f) len.n[f] = n_valid[f];
+    hipLaunchKernelGGL(k_sht_twiddle, dim3((P + 255) / 256), dim3(256), 0, ctx->stream, P, S.tw);
+    QF_HIP(hipGetLastError());
+    // rows 2L..K-1 of At meet zero twiddles; zeroed so that nothing stale (a NaN of an earlier call) enters the sums
+    if (K > 2 * L) QF_HIP(hipMemsetAsync(S.At + (size_t)2 * L * ldA, 0, (size_t)(K - 2 * L) * ldA * sizeof(double), ctx->stream));
+    switch (nf) {
+    case 1: QF_TRY(launch_fields<1>(ctx, L, len, omega_dev, ldA)); break;
+    case 2: QF_TRY(launch_fields<2>(ctx, L, len, omega_dev, ldA)); break;
+    case 3: QF_TRY(launch_fields<3>(ctx, L, len, omega_dev, ldA)); break;
+    case 4: QF_TRY(launch_fields<4>(ctx, L, len, omega_dev, ldA)); break;
+    default: qf_set_error("qf_launch_sht_fields: %d fields (1..4)", nf); return QF_ERR_INVALID;
+    }
+    const dim3 gf((P + SHT_BN - 1) / SHT_BN, ldA / SHT_BM);
+    hipLaunchKernelGGL(k_sht_fourier_fields, gf, dim3(256), 0, ctx->stream, L, M, K, S.At, ldA, S.tw, S.f, f32mask);
     QF_HIP(hipGetLastError());
     return QF_OK;
 }

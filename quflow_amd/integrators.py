@@ -1185,6 +1185,31 @@ class DeviceTrajectory:
         _lib.check(self._lib.qf_shr2fun(self.ctx.handle, None, ctypes.c_longlong(n), L, int(bool(berezin)), ptr(f)))
         return f
 
+    def fields(self, qutypes):
+        """The function-space outputs of the resident state, {qutype: array}: `qutypes` is a dict in the reference's form
+        restricted to 'fun', 'funL2', 'funhalf', 'funL2half' with dtypes float32 / float64 (simulation.py:313-342).  Each
+        grid is `self.fun(n_omega, berezin).astype(dtype)` bit for bit ('half': n_omega = (N//2)**2, 'L2': berezin=False),
+        but the state goes through mat2shr once, the fields of one bandwidth share one synthesis and the cast happens on
+        the device (qf_state_fields): a float32 grid crosses PCIe as float32.  The state, the carried increment and the
+        statistics of the run are untouched: the next `advance` continues bit for bit as if the call had not happened."""
+        from .transforms import _fields_call
+        self._double_only("fields")
+        self._need_basis()
+        return _fields_call(self.ctx, None, self.N, qutypes)
+
+    def fields_and_shr(self, qutypes):
+        """(self.fields(qutypes), self.shr()), bit for bit, for a record that stores both: when the sweep that made the
+        fields has left mat2shr of the whole state on the device (a field of the full bandwidth with a resident basis, or
+        swept last with a streamed one) the coefficients are copied out (qf_shr_held) instead of swept again.  The library
+        decides: QF_ERR_STATE from qf_shr_held means the device copy holds fewer coefficients, and `shr()` sweeps."""
+        out = self.fields(qutypes)
+        omega = np.zeros(self.N * self.N, dtype=np.float64)
+        rc = self._lib.qf_shr_held(self.ctx.handle, ptr(omega), ctypes.c_longlong(omega.shape[0]))
+        if rc == 4:                       # QF_ERR_STATE
+            return out, self.shr()
+        _lib.check(rc)
+        return out, omega
+
     def spectral_budget(self, lmax=None, coefficients=False):
         """quflow_amd.analysis.spectral_budget of the resident state with what is installed on this trajectory -- its
         Hamiltonian, its forcing (of a StochasticForcing only the affine terms a_W, a_P, a_lap: the noise pattern belongs
@@ -1361,6 +1386,10 @@ class DeviceStackTrajectory:
     def fun(self, j, n_omega=None, berezin=True):
         """DeviceTrajectory.fun of member j."""
         return self._select(j).fun(n_omega, berezin)
+
+    def fields(self, j, qutypes):
+        """DeviceTrajectory.fields of member j."""
+        return self._select(j).fields(qutypes)
 
     def spectral_budget(self, j, lmax=None, coefficients=False):
         """DeviceTrajectory.spectral_budget of member j (the built-in Hamiltonian, no forcing)."""

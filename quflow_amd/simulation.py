@@ -27,8 +27,12 @@ and only what the output needs comes down.  Restarting from `Simulation(filename
 bit-identically (tests/test_simulation.py:130-168: the stepper restarts its iteration vector at every
 chunk anyway, isospectral.py:430).
 
-Function-space outputs ('fun', 'funL2') are not written by Simulation; the synthesis itself is quflow_amd.transforms
-(shr2fun, DeviceTrajectory.fun).
+Function-space outputs -- the reference's 'fun', 'funL2' (its defaults, simulation.py:40), 'funhalf', 'funL2half' -- are
+written by `Simulation(..., function_space=True)`: rows under the reference's variable names ('funhalf' -> fun,
+'funL2half' -> funL2), real float32 / float64 only, formed on the device by one call per state (qf_state_fields: one sweep
+of the basis, one stacked synthesis per bandwidth, the cast on the device; `transforms.state_fields`,
+`DeviceTrajectory.fields`).  The keyword is opt-in because the record class otherwise never touches a GPU; without it such
+a qutype is refused at construction, and a file the reference wrote with its defaults can be read but not appended to.
 """
 import base64
 import datetime
@@ -45,6 +49,8 @@ from .geometry import hbar
 
 _default_qutypes = {'mat': None}
 _qutype2varname = {'mat': 'mat', 'shr': 'shr', 'shc': 'shc'}
+# function-space qutypes (written with function_space=True only) and their variables, simulation.py:41
+_function_varname = {'fun': 'fun', 'funhalf': 'fun', 'funL2': 'funL2', 'funL2half': 'funL2'}
 _pickled_argnames = ['qutypes', 'hamiltonian', 'forcing', 'integrator', 'callback', 'integrator_callback',
                      'strang_splitting']          # simulation.py:53
 _info_args = ['info']
@@ -307,14 +313,30 @@ def store_exists(filename):
 # the simulation record
 # ------------------------------------------------------------------------------------------------
 
+def _state_fields(W, qutypes):
+    """The one place a record fetches function-space rows of a host state from: {qutype: array} for a matrix, (k, L, 2L-1)
+    arrays for a (k,N,N) stack (quflow_amd.transforms.state_fields, on the device)."""
+    from .transforms import state_fields
+    return state_fields(W, qutypes)
+
+
+def _refuse_function_space(qutype, what):
+    raise NotImplementedError("qutype '%s' (function-space output, quflow/transforms.py) is written only by "
+                              "Simulation(..., function_space=True), which forms the rows on the device: %s"
+                              % (qutype, what))
+
+
 class Simulation:
     """Counterpart of quflow.QuSimulation (simulation.py:60-478): output record, checkpoint and
-    callback of `solve` in one object.  See the module docstring for the layout."""
+    callback of `solve` in one object.  See the module docstring for the layout.
+    function_space=True: the qutypes 'fun', 'funL2', 'funhalf', 'funL2half' (real dtypes) are accepted, at creation and on
+    a re-opened record, and their rows come from the device."""
 
     def __init__(self, filename, overwrite=False, state=None, time=None, qutypes=None, loggers=None, datapath="/",
-                 **kwargs):
+                 function_space=False, **kwargs):
         from . import __version__
         self.filename = str(filename)
+        self.function_space = bool(function_space)
         if datapath[-1] != "/":
             raise ValueError("Datapath must end with /")
         self.datapath = datapath
@@ -324,9 +346,13 @@ class Simulation:
                 raise ValueError("At least `state` must be provided to initialize a Simulation.")
             self.qutypes = dict(_default_qutypes if qutypes is None else qutypes)
             for q in self.qutypes:
-                if q not in _qutype2varname:
-                    raise NotImplementedError("qutype '%s' (function-space output, quflow/transforms.py) is outside "
-                                              "this package; available: %s" % (q, sorted(_qutype2varname)))
+                if q in _function_varname:
+                    if not self.function_space:
+                        _refuse_function_space(q, "without the keyword the available qutypes are %s" % sorted(_qutype2varname))
+                elif q not in _qutype2varname:
+                    raise NotImplementedError("qutype '%s' is outside this package; available: %s"
+                                              % (q, sorted(_qutype2varname) + sorted(_function_varname)))
+            self._function_dtypes()
             self.store = open_store(filename, True, datapath)
             self.store.set_attr("attrs", "version", __version__)
             self.store.set_attr("attrs", "created", datetime.datetime.now().isoformat())
@@ -347,9 +373,30 @@ class Simulation:
                 self.loggers = _loads(self.store.get_attr("attrs", "loggers"))
 
     # ---- representations of the state (simulation.py:285-343, the matrix and coefficient forms)
-    def _representations(self, W, device_shr=None):
+    def _function_dtypes(self):
+        """The function-space qutypes of this record as {qutype: dtype}, checked (the reference's two ValueErrors, real
+        dtypes only); empty without the keyword."""
+        if not self.function_space:
+            return {}
+        from .transforms import check_function_qutypes
+        return check_function_qutypes(self.qutypes)
+
+    def _representations(self, W, device_shr=None, device_fields=None):
         N = W.shape[-1]
+        fields, want = None, self._function_dtypes()
+        for qutype in self.qutypes:
+            if qutype in _function_varname and not self.function_space:
+                # (a file the reference wrote with its default qutypes holds 'fun' / 'funL2' rows: reading them works)
+                _refuse_function_space(qutype, "'%s' can be read but not appended to without it" % self.filename)
         for qutype, dtype in self.qutypes.items():
+            if qutype in _function_varname:
+                if fields is None:         # every function-space row of the state from one call
+                    fields = device_fields if device_fields is not None else _state_fields(W, want)
+                arr = np.squeeze(np.asarray(fields[qutype]))
+                if arr.dtype != want[qutype]:
+                    raise TypeError("function-space row '%s' came back as %s, the record holds %s" % (qutype, arr.dtype, want[qutype]))
+                yield _function_varname[qutype], arr, qutype
+                continue
             if qutype == 'mat':
                 arr = W.astype(W.dtype if dtype is None else dtype)
             elif qutype == 'shr':
@@ -358,10 +405,8 @@ class Simulation:
                 arr = np.squeeze(np.array(rows))
                 arr = arr.astype(W.real.dtype if dtype is None else dtype)
             elif qutype != 'shc':
-                # (a file the reference wrote with its default qutypes holds 'fun' / 'funL2' rows: reading them works,
-                # appending would need the spherical-harmonics synthesis of quflow/transforms.py)
-                raise NotImplementedError("qutype '%s' (function-space output, quflow/transforms.py) is outside this "
-                                          "package: '%s' can be read but not appended to" % (qutype, self.filename))
+                raise NotImplementedError("qutype '%s' is outside this package: '%s' can be read but not appended to"
+                                          % (qutype, self.filename))
             else:
                 from .quantization import mat2shc
                 arr = np.squeeze(np.array([mat2shc(Wi) for Wi in W.reshape((-1, N, N))]))
@@ -369,7 +414,7 @@ class Simulation:
             yield _qutype2varname[qutype], arr, qutype
 
     def _initialize_fields(self, W, time, fields):
-        for varname, arr, qutype in self._representations(W):
+        for varname, arr, qutype in list(self._representations(W)):      # (every row first, as in __call__)
             self.store.create(varname, arr)
         self.store.set_attr("attrs", "N", int(W.shape[-1]))
         self.store.create("time", np.float64(time))
@@ -385,9 +430,9 @@ class Simulation:
             self.store.create(name, np.asarray(value))
 
     # ---- the callback protocol of solve (simulation.py:433-478)
-    def __call__(self, W, delta_time, delta_steps=1, device_shr=None, **kwargs):
+    def __call__(self, W, delta_time, delta_steps=1, device_shr=None, device_fields=None, **kwargs):
         W = np.asarray(W)
-        rows = list(self._representations(W, device_shr))      # every row first: a refused qutype appends nothing
+        rows = list(self._representations(W, device_shr, device_fields))      # every row first: a refused qutype appends nothing
         for varname, arr, qutype in rows:
             self.store.append(varname, arr)
         self.store.append("time", self.store.read("time", -1) + delta_time)
@@ -707,11 +752,9 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
         tr = _int.DeviceStackTrajectory(W, magnetic=(kind == 'mhd'))
         adv_kw = {k: ikw[k] for k in ("tol", "maxit", "minit", "reinitialize") if k in ikw}
     stack_kind = kind if kind in ('stack', 'mhd') else None
-    want_shr = any(isinstance(c, Simulation) and 'shr' in c.qutypes for c in (callback or ()))
     try:
         for k0 in range(0, steps, max(steps_out, 1)):
             n = min(steps_out, steps - k0)
-            extra = {}
             if tr is not None:
                 st = tr.advance(dt, n, **adv_kw)
                 W = tr.download()
@@ -723,8 +766,6 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
                         ikw['stats']['tol' if stack_kind == 'mhd' else 'tol_auto'] = st["tol"]
                     ikw['stats']['iterations'] = st["iterations"]
                     ikw['stats']['maxit' if stack_kind == 'mhd' else 'number_of_maxit'] = st["number_of_maxit"]
-                if want_shr and stack_kind is None and not tr.c64:
-                    extra["device_shr"] = [tr.shr()]        # mat2shr on the resident state: N^2 doubles over PCIe
             else:
                 W = integrator(W, dt, steps=n, **ikw)
             delta_time = n * dt
@@ -735,7 +776,25 @@ def solve(W, dt=None, stepsize=None, steps=None, simtime=None, endtime=None, ste
                 if 'stats' in ikw:
                     callback_kwargs.update(ikw['stats'])
                 if isinstance(cfun, Simulation):
-                    cfun(W, delta_time=delta_time, delta_steps=n, **extra, **callback_kwargs)
+                    more = {}
+                    if tr is not None and not getattr(tr, "c64", False):
+                        # rows from the resident state in double precision (a complex64 resident run and the host path go
+                        # through the array the callback receives).  'shr': mat2shr on the device, N^2 doubles over PCIe.
+                        # Function-space rows: one sweep of the basis, one stacked synthesis per bandwidth, and only the
+                        # grids cross PCIe, in their dtype; an 'shr' row next to them shares that sweep where it can.
+                        want_fun = cfun._function_dtypes()
+                        want_shr = 'shr' in cfun.qutypes and stack_kind is None
+                        if want_fun and want_shr:
+                            more["device_fields"], omega = tr.fields_and_shr(want_fun)
+                            more["device_shr"] = [omega]
+                        elif want_shr:
+                            more["device_shr"] = [tr.shr()]
+                        elif want_fun and stack_kind is None:
+                            more["device_fields"] = tr.fields(want_fun)
+                        elif want_fun:
+                            members = [tr.fields(j, want_fun) for j in range(tr.k)]
+                            more["device_fields"] = {q: np.array([m[q] for m in members]) for q in want_fun}
+                    cfun(W, delta_time=delta_time, delta_steps=n, **more, **callback_kwargs)
                 else:
                     cfun(W, delta_time=delta_time, delta_steps=n, **callback_kwargs)
             # a StochasticForcing carries the counter of its noise: the record a resumed run starts from follows it

@@ -4,6 +4,8 @@ Mirrors `quflow.transforms` (quflow/transforms.py) with the reference's names an
 
   * `shr2fun`, `shc2fun` -- synthesis onto the MW grid (L, 2L-1) at bandwidth L: hand-written HIP kernels behind the C ABI
     (qf_shr2fun / qf_shc2fun, quflow_amd/csrc/sht.hip), where the reference calls pyssht or ducc0 (neither is needed here);
+  * `state_fields` -- the function-space output rows of a state ('fun', 'funL2', 'funhalf', 'funL2half' of
+    quflow/simulation.py:313-342) from one sweep of the basis and one stacked synthesis per bandwidth (qf_state_fields);
   * `as_fun`, `as_shr` -- the reference's dispatch on the kind of data;
   * `shr2shc`, `shc2shr`, `sphgrid`, `fun2img`, `img2fun` -- host numpy, as in the reference (vectorised).
 
@@ -158,6 +160,83 @@ def shr2fun(omega, N=-1, berezin=True, device=None):
     ctx = get_context(max(L, 2), device)
     _lib.check(ctx._lib.qf_shr2fun(ctx.handle, ptr(om), ctypes.c_longlong(om.shape[0]), L, int(bool(berezin)), ptr(f)))
     return f
+
+
+# ---- function-space output of a state: the reference's 'fun' / 'funL2' / 'funhalf' / 'funL2half' qutypes
+# (quflow/simulation.py:41, 313-342): the variable a row is stored under
+FUNCTION_VARNAMES = {'fun': 'fun', 'funhalf': 'fun', 'funL2': 'funL2', 'funL2half': 'funL2'}
+
+
+def field_spec(qutype, N):
+    """(n_omega, berezin, variable name) of a function-space qutype for an N x N state: 'half' keeps the leading
+    (N//2)**2 coefficients (simulation.py:336-337), 'L2' switches the Berezin multipliers off (:338-339)."""
+    if qutype not in FUNCTION_VARNAMES:
+        raise KeyError("'%s' is not a function-space qutype; available: %s" % (qutype, sorted(FUNCTION_VARNAMES)))
+    n_omega = (N // 2) ** 2 if 'half' in qutype else N * N
+    return n_omega, 'L2' not in qutype, FUNCTION_VARNAMES[qutype]
+
+
+def check_function_qutypes(qutypes):
+    """The function-space part of a qutypes dict as {qutype: numpy dtype}, checked: the reference's two ValueErrors for
+    'fun' + 'funhalf' and 'funL2' + 'funL2half' (simulation.py:122-126, both rows would go to one variable), real dtypes
+    float32 / float64 only (None: float64, what the reference's np.array(..., dtype=None) makes).  A complex dtype is
+    refused: the reference's branch for it hands real coefficients to shc2fun, which is not mirrored."""
+    if 'fun' in qutypes and 'funhalf' in qutypes:
+        raise ValueError("Cannot have both fun and funhalf outputs.")
+    if 'funL2' in qutypes and 'funL2half' in qutypes:
+        raise ValueError("Cannot have both funL2 and funL2half outputs.")
+    out = {}
+    for q, dtype in qutypes.items():
+        if q not in FUNCTION_VARNAMES:
+            continue
+        dt = np.dtype(np.float64 if dtype is None else dtype)
+        if dt.kind == 'c':
+            raise NotImplementedError("qutype '%s' with the complex dtype %s: complex function-space rows are not written "
+                                      "(use float32 or float64)" % (q, dt))
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise NotImplementedError("qutype '%s' with dtype %s: function-space rows are float32 or float64" % (q, dt))
+        out[q] = dt
+    return out
+
+
+def _fields_call(ctx, W, N, qutypes):
+    """qf_state_fields on `ctx` for the state W (None: the resident state): {qutype: (L, 2L-1) array}."""
+    qutypes = dict(qutypes)
+    unknown = [q for q in qutypes if q not in FUNCTION_VARNAMES]
+    if unknown:
+        raise KeyError("not function-space qutypes: %s; available: %s" % (unknown, sorted(FUNCTION_VARNAMES)))
+    dtypes = check_function_qutypes(qutypes)
+    if not dtypes:
+        return {}
+    specs = (_lib.Field * len(dtypes))()
+    outs, ptrs = {}, (ctypes.c_void_p * len(dtypes))()
+    for i, (q, dt) in enumerate(dtypes.items()):
+        n_omega, berezin, _ = field_spec(q, N)
+        if n_omega < 1:
+            raise ValueError("qutype '%s' keeps (N//2)**2 = 0 coefficients at N=%d" % (q, N))
+        L = _bandwidth(n_omega, -1)
+        specs[i] = _lib.Field(n_omega, int(berezin), 1 if dt == np.dtype(np.float32) else 0)
+        outs[q] = np.empty((L, 2 * L - 1), dtype=dt)
+        ptrs[i] = outs[q].ctypes.data
+    _lib.check(ctx._lib.qf_state_fields(ctx.handle, None if W is None else ptr(W), len(dtypes), specs, ptrs))
+    return outs
+
+
+def state_fields(W, qutypes, device=None):
+    """The function-space outputs of a state, {qutype: array}: for each of 'fun', 'funL2', 'funhalf', 'funL2half' in
+    `qutypes` (a dict {qutype: float32 / float64}, the reference's form) the grid shr2fun(mat2shr(W)[:n], berezin=...) cast
+    to its dtype, bit for bit, from ONE sweep of the basis and one stacked synthesis per bandwidth (qf_state_fields); the
+    cast happens on the device, so a float32 grid crosses PCIe as float32.  W: an (N,N) complex matrix, or a (k,N,N) stack,
+    whose fields come back as (k, L, 2L-1) arrays, member by member."""
+    W = np.asarray(W)
+    assert np.iscomplexobj(W), "W must be a complex array."
+    N = W.shape[-1]
+    if W.ndim == 3:
+        rows = [state_fields(Wi, qutypes, device) for Wi in W]
+        return {q: np.array([r[q] for r in rows]) for q in (rows[0] if rows else {})}
+    Wc = np.ascontiguousarray(W, dtype=np.complex128)
+    from .quantization import _transform_context
+    return _fields_call(_transform_context(N, device), Wc, N, qutypes)
 
 
 def as_fun(data, N=-1, **kwargs):
