@@ -531,6 +531,42 @@ int qf_isomp_diag(qf_ctx *ctx, double dt, int steps, double tol, int minit, int 
 /* matrix infinity norm of the state, np.linalg.norm(W, inf) (isospectral.py:448) */
 int qf_norm_inf_W(qf_ctx *ctx, double *out);
 
+/* ---- Casimirs: out[k-1] = C_k(W) = Re tr((iW)^k) / N for k = 1..kmax, 1 <= kmax <= 8 -- what the isospectral steppers
+ *      conserve (csrc/casimir.hip).  Defined for ANY complex W: nothing assumes a skew-Hermitian matrix, a
+ *      host matrix with rounding in its symmetry gets the trace of its actual powers, as np.trace of numpy's products.
+ *      C_2 = <W, W> = 2 enstrophy.  complex128 arithmetic.
+ *      The powers A_j = W^j for j <= p = ceil(kmax / 2) are stored: A_2 = W W, A_3 = A_2 W, A_4 = A_2 A_2, at most three plain
+ *      products of the stepper's own product kernel, into the per-iteration staging matrices Whalf, Phalf, PW (a host-in W and
+ *      a widened complex64 state go to `stage`; all free between stepper calls).  Then tr(W^(i+j)) = sum_ab (A_i)_ab (A_j)_ba
+ *      with i = floor(k / 2), j = k - i (k = 1: the diagonal of W; k = 2 needs no product), all pair sums from ONE pass of one
+ *      kernel (k_power_traces) over the stored powers: a workgroup reads the tiles (I,J) and (J,I) of every power once, every
+ *      thread and every level of the reduction tree carries a two-sum compensation term, block partials are added by a second
+ *      one-block launch in fixed order -- no float atomics, two calls return the same bits.  The phase i^k and the real part
+ *      are applied to the raw sum on the host, followed by a true division by N.
+ *      On matrices whose entries have integer real and imaginary parts the result is exact whenever 4 tr(|W|^k) < 2^53.
+ *      Every form leaves the run untouched -- the state W, the carried increment (qf_isomp_continue), the stack and its
+ *      increments, the device copy of the coefficients, the stochastic counter -- and a resident run continues bit for bit as
+ *      if the call had not happened.
+ *      QF_ERR_INVALID for kmax outside 1..8, a null output or a member index out of range, QF_ERR_STATE without the resident
+ *      state or stack the form reads -- each before anything is launched; QF_ERR_NONFINITE when a returned sum is inf or NaN
+ *      (an inf or NaN entry of the matrix). ---- */
+/* W_host: N x N complex128, or NULL for the context's resident complex128 state.  out: kmax doubles. */
+int qf_casimirs(qf_ctx *ctx, const void *W_host, int kmax, double *out);
+/* The resident complex64 state (qf_c64_upload_W), widened on the device to complex128 -- exact -- into `stage`, then the
+ * double path above: the instrument stays below the float32 stepper's own drift. */
+int qf_c64_casimirs(qf_ctx *ctx, int kmax, double *out);
+/* Member j of the resident stack (qf_states_upload), read in place. */
+int qf_states_casimirs(qf_ctx *ctx, int j, int kmax, double *out);
+/* The resident MHD pair (W, Theta), k == 2 (else QF_ERR_INVALID), what magmp conserves:
+ *   magnetic[k-1] = C_k(Theta), k = 1..kmax;
+ *   cross[k-1]    = Re tr((iW)(iTheta)^k) / N, k = 1..p = ceil(kmax / 2) -- the members of the cross-helicity family that the
+ *                   stored powers of Theta give without a further product; W is read in place.
+ * magnetic[1] = 2 magnetic_casimir and cross[0] = cross_helicity of qf_mhd_diagnostics. */
+int qf_mhd_casimirs(qf_ctx *ctx, int kmax, double *magnetic, double *cross);
+/* HIP-event times of this context's most recent completed call of the four above, in milliseconds: the products that
+ * stored the powers (0 for kmax <= 2), and the traces kernel with its fold.  QF_ERR_STATE before the first one. */
+int qf_casimirs_times(qf_ctx *ctx, double *products_ms, double *traces_ms);
+
 /* ---- Hermitian eigendecomposition H = V diag(lambda) V^H on the device (csrc/eigh.hip): parallel one-sided Jacobi on
  *      H + 2 |H|_inf I, eigenvalues refined by their Rayleigh quotients with H.  complex128 only.  lambda: N doubles,
  *      ascending; V: (N,N) complex128, unitary, column j belongs to lambda[j].  Deterministic: two calls return the same

@@ -174,6 +174,11 @@ SIGNATURES = {
     "qf_fun2shr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp]),
     "qf_diagnostics": (ctypes.c_int, [_vp, _dp, _dp]),
     "qf_norm_inf_W": (ctypes.c_int, [_vp, _dp]),
+    "qf_casimirs": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp]),
+    "qf_c64_casimirs": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
+    "qf_states_casimirs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp]),
+    "qf_mhd_casimirs": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp]),
+    "qf_casimirs_times": (ctypes.c_int, [_vp, _dp, _dp]),
     "qf_eigh": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(EighStats)]),
     "qf_eigh_skew": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(EighStats)]),
     "qf_eigh_state": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(EighStats)]),

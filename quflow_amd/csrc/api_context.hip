@@ -248,6 +248,9 @@ int qf_ctx_destroy(qf_ctx *ctx)
     for (cplx *p : ctx->stack)
         if (p) (void)hipFree(p);
     if (ctx->mhd_part) (void)hipFree(ctx->mhd_part);
+    if (ctx->cas_part) (void)hipFree(ctx->cas_part);
+    for (hipEvent_t e : ctx->cas_ev)
+        if (e) (void)hipEventDestroy(e);
     for (int q = 0; q < 4; ++q) {
         if (ctx->oz_planes[q]) (void)hipFree(ctx->oz_planes[q]);
         if (ctx->oz_scale[q]) (void)hipFree(ctx->oz_scale[q]);
@@ -336,6 +339,7 @@ int qf_c64_upload_W(qf_ctx *ctx, const void *W_host)
     QF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->c64->increment_valid = false;
     ctx->c64->w_skew_known = false;
+    ctx->c64->w_set = true;
     return QF_OK;
 }
 

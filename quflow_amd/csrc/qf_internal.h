@@ -239,6 +239,7 @@ __device__ __forceinline__ C2 qf_laplace_entry(int N, const C2 *__restrict__ P, 
 // double) is the double-precision path's.
 struct qf_c64 {
     float2 *W = nullptr;                       // state
+    bool w_set = false;                        // a state has been put into W (qf_c64_upload_W)
     float2 *dW[2] = {nullptr, nullptr};        // iteration vector, ping-pong
     float2 *Whalf = nullptr, *Phalf = nullptr, *PW = nullptr;
     float2 *kahan_c = nullptr;                 // compensation term (compsum), on demand
@@ -414,6 +415,11 @@ struct qf_ctx {
     std::vector<cplx *> stack;
     int stack_k = 0;
     double *mhd_part = nullptr;  // k_mhd_sums: 5 x 1024 block partials, then the five sums (on demand)
+    // qf_casimirs and its kin (casimir.hip), on demand: k_power_traces' (sum, compensation) pairs of up to 12 sums x 1024
+    // blocks, then the folded sums; events before the products, between products and traces, and behind the traces
+    double *cas_part = nullptr;
+    hipEvent_t cas_ev[3] = {nullptr, nullptr, nullptr};
+    bool cas_timed = false;      // cas_ev[] were recorded by a completed call (qf_casimirs_times)
     // qf_mhd_spectral_budget's own buffers (first call, kept): P, B and the three tendencies (5 N^2 complex, readable through
     // qf_download_buffer); the five packed diagonals and five sweep results (10 x N(N+1)/2 complex; the coefficient arrays
     // overlay the packed diagonals once the sweep is over); the nine rows

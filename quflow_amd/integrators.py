@@ -1117,6 +1117,18 @@ class DeviceTrajectory:
         _lib.check(fn(self.ctx.handle, ctypes.byref(e), ctypes.byref(s)))
         return e.value, s.value
 
+    def casimirs(self, kmax=4):
+        """C_k = Re tr((iW)^k) / N, k = 1..kmax <= 8, of the resident state: the (kmax,) array quflow_amd.physics.casimirs
+        gives for `download()`, without the download (qf_casimirs; a complex64 state is widened on the device and summed in
+        double, qf_c64_casimirs).  At most three products and one reduction pass, cheap enough to log per chunk.  The state,
+        the carried increment and the statistics of the run are untouched: the next `advance` continues bit for bit as if
+        the call had not happened."""
+        from .physics import casimirs_call, check_kmax
+        kmax = check_kmax(kmax)
+        if self.c64:
+            return casimirs_call(self._lib.qf_c64_casimirs, kmax, self.ctx.handle)
+        return casimirs_call(self._lib.qf_casimirs, kmax, self.ctx.handle, None)
+
     def _need_basis(self):
         """The transforms' mode on this trajectory's context, by quantization.use_streamed: above the resident limit
         (N > 2048 by default) the blocks are rebuilt slab by slab for each call, else the basis is computed once."""
@@ -1375,6 +1387,26 @@ class DeviceStackTrajectory:
         _lib.check(self._lib.qf_states_inner(self.ctx.handle, m))
         return {"energy": e, "enstrophy": s, "members": [(m[2 * j], m[2 * j + 1]) for j in range(self.k)]}
 
+    def casimirs(self, j, kmax=4):
+        """DeviceTrajectory.casimirs of member j, read in place (qf_states_casimirs): the context's state W is not used."""
+        from .physics import casimirs_call, check_kmax
+        kmax = check_kmax(kmax)
+        return casimirs_call(self._lib.qf_states_casimirs, kmax, self.ctx.handle, int(j))
+
+    def mhd_casimirs(self, kmax=4):
+        """What magmp conserves besides the energy, of the resident pair (W, Theta) (qf_mhd_casimirs):
+        {"magnetic": C_k(Theta) for k = 1..kmax, "cross": Re tr((iW)(iTheta)^k) / N for k = 1..ceil(kmax / 2)}.
+        magnetic[1] = 2 magnetic_casimir and cross[0] = cross_helicity of `diagnostics()`.  The run is untouched."""
+        from .physics import check_kmax
+        kmax = check_kmax(kmax)
+        if not self.magnetic or self.k != 2:
+            raise ValueError("mhd_casimirs are those of the MHD pair (W, Theta): this stack is not magnetic (k=%d)" % self.k)
+        mag = np.empty(kmax, dtype=np.float64)
+        cross = np.empty((kmax + 1) // 2, dtype=np.float64)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(self._lib.qf_mhd_casimirs(self.ctx.handle, kmax, mag.ctypes.data_as(dp), cross.ctypes.data_as(dp)))
+        return {"magnetic": mag, "cross": cross}
+
     def _select(self, j):
         _lib.check(self._lib.qf_states_select(self.ctx.handle, int(j)))
         return self._member
@@ -1511,6 +1543,12 @@ class DeviceEnsemble:
 
     def diagnostics(self):
         return [m.diagnostics() for m in self.members]
+
+    def casimirs(self, kmax=4):
+        """(members, kmax) array: DeviceTrajectory.casimirs of every member, member by member as `diagnostics()`."""
+        from .physics import check_kmax
+        kmax = check_kmax(kmax)
+        return np.stack([m.casimirs(kmax) for m in self.members])
 
     def download(self):
         return [m.download() for m in self.members]

@@ -31,6 +31,38 @@ def enstrophy(W):
     return _diagnostics(W)[1]
 
 
+CASIMIR_KMAX = 8
+
+
+def check_kmax(kmax):
+    """The highest Casimir asked for as an int in 1..8; ValueError otherwise (before anything touches a device)."""
+    if isinstance(kmax, bool) or not isinstance(kmax, (int, np.integer)) or not 1 <= kmax <= CASIMIR_KMAX:
+        raise ValueError("kmax must be an integer in 1..%d, got %r" % (CASIMIR_KMAX, kmax))
+    return int(kmax)
+
+
+def casimirs_call(fn, kmax, *args):
+    """One of the qf_*casimirs entry points with its trailing (kmax, out) arguments: the (kmax,) ndarray.  An inf or NaN
+    in the matrix raises ValueError (QF_ERR_NONFINITE)."""
+    out = np.empty(kmax, dtype=np.float64)
+    _lib.check(fn(*args, kmax, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out
+
+
+def casimirs(W, kmax=4):
+    """The Casimirs C_k = Re tr((iW)^k) / N, k = 1..kmax <= 8, of a host matrix, formed on the device (qf_casimirs): an
+    ndarray of shape (kmax,).  Any complex W -- nothing assumes skew-Hermitian symmetry; complex64 input is computed in
+    complex128.  C_2 = <W, W> = 2 enstrophy(W).  What the isospectral steppers conserve; a `Simulation` logger as it
+    stands.  A stack (..., N, N) is read at its first member, as energy_euler and enstrophy do."""
+    kmax = check_kmax(kmax)
+    W = np.asarray(W)
+    if W.ndim >= 3:
+        W = W[(0,) * (W.ndim - 2) + (Ellipsis,)]
+    Wc = as_c128(W, "W")
+    ctx = get_context(Wc.shape[-1])
+    return casimirs_call(ctx._lib.qf_casimirs, kmax, ctx.handle, ptr(Wc))
+
+
 def mhd_diagnostics(state):
     """The diagnostics of the MHD state (W, Theta), a (2,N,N) array, in one device call (qf_mhd_diagnostics: one Poisson
     solve, one reduction pass): a dict with energy_kinetic = -<W, Delta^-1 W>/2, energy_magnetic = -<Theta, Delta Theta>/2,

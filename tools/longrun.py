@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """BASELINE.json config 5: N=2048 fp64 long-time run (10k steps) on one MI355X, with the
-conservation record (energy, enstrophy, Casimirs via host eigen-free traces every chunk).
+conservation record: energy, enstrophy and the Casimir drift for k = 2, 3, 4 every chunk, from the device
+(tr.casimirs(4)); the end-of-run Casimir drift from host traces of the downloaded state stands next to it.
 stdout = one JSON object (redirect it into profiles/); per-chunk progress lines go to stderr."""
 import json
 import sys
@@ -33,6 +34,7 @@ def main():
     tr = qfa.DeviceTrajectory(W0)
     e0, s0 = tr.diagnostics()
     c0 = casimirs(W0.astype(np.complex128))
+    cd0 = tr.casimirs(4)
     rows = []
     t0 = time.perf_counter()
     tgpu = 0.0
@@ -42,7 +44,9 @@ def main():
         tr.sync()
         tgpu += time.perf_counter() - t1
         e, s = tr.diagnostics()
+        cd = tr.casimirs(4)
         rows.append({"step": k + chunk, "energy_drift": e - e0, "enstrophy_drift": s - s0,
+                     "casimir_drift_k234": [float(a - b) for a, b in zip(cd[1:], cd0[1:])],
                      "iterations": st["iterations"], "number_of_maxit": st["number_of_maxit"]})
         print(json.dumps(rows[-1]), file=sys.stderr, flush=True)     # progress; stdout carries ONE JSON object
     W = tr.download()
@@ -69,6 +73,7 @@ def main():
     out = {"N": N, "dtype": "complex64" if c64 else "complex128", "steps": steps, "chunk": chunk, "stepsize": 0.25, "timesteps_per_s": steps / tgpu,
            "wall_s": time.perf_counter() - t0, "energy0": e0, "enstrophy0": s0,
            "casimir_drift_k234": [a - b for a, b in zip(c1, c0)],
+           "casimir_drift_k234_device": rows[-1]["casimir_drift_k234"] if rows else None,
            "skew_hermitian_defect": float(np.abs(W + W.conj().T).max()), "trace": complex(np.trace(W)).__repr__(),
            "roofline": roof, "chunks": rows}
     print(json.dumps(out))
